@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- entities/sec through cull + transform on the BASELINE.json workload.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 A step is ONE FRAME of the hot path over the resident world, as a frame loop that draws every frame sees it:
 re_cull_pack (visibility query over the spatial hash + frustum / logic cull + instance pack, with the
@@ -10,8 +10,10 @@ kinematic / TRS->mat4 tick) -- Pipeline::execute of the reference (flows/pipelin
 synchronous.  Inputs are resident in HBM before the timed region starts.
 
 N=1: BASELINE.json configs[1] -- 10,077,696 static entities, one per level-0 world section (uniform spatial-hash
-fill), one camera frustum, far = 1000.  `value` = entities / median frame time (SURVEY 8d: median of >= 100 frames);
-`ms_per_step` = wall time of exactly K timed frames / K.  The same run also reports, as labelled extras: the
+fill), one camera frustum, far = 1000.  `value` = entities / median frame time of the K timed frames (median of
+>= 100 frames, so K >= 100); `ms_per_step` = wall time of exactly K timed frames / K.  --dump-outputs DIR writes what the last
+timed frame returned to its caller as DIR/<name>.npy (inputs are synthetic and fixed: two builds compare output for output).
+The same run also reports, as labelled extras: the
 pipelined throughput of asynchronous frames, far = 8192 (wide frustum, ~500 K instances: the large pack path),
 configs[2] (100,777 rotating bodies: tick + cull) incl. a tick of every dynamic entity, configs[4] (deferred
 lighting), the CPU rows, and a full-size check of the visible set against the CPU oracle.
@@ -36,9 +38,12 @@ SLAB_INSTANCES = 4096          # all-gather slab per rank and frame (instances);
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s spec, ~6.3 TB/s achievable)
 VALU_PEAK_TFLOPS = 157.3       # fp32 vector peak (MI355X_MICROARCH.md), the bound of the lighting kernel
 PER_GPU_AXIS = 216             # 216^3 = 10,077,696 sections/entities per GPU
-MEDIAN_FRAMES = 128            # median of >= 100 frames
 K1_MIN_LAUNCHES = 96           # launches of the dominant kernel timed with HIP events, whatever --steps is
 CLOCK_WARMUP_FRAMES = 8000     # untimed asynchronous frames (~7 us each) in front of the warm-up steps: the run starts on an idle-clock GPU
+DUMP_MAX_BYTES = 64_000_000    # --dump-outputs: everything written, at most
+DUMP_MAX_INSTANCES = 700_000   # visible instances written (80 B each: id, matrix, row index); a seeded sample beyond that
+DUMP_PIXELS = 1 << 20          # lighting: pixels of the 4096 x 4096 image written (a seeded sample, 24 B each)
+DUMP_SEED = 0
 
 
 def parse():
@@ -58,7 +63,14 @@ def parse():
     ap.add_argument("--cpu-sample-axis", type=int, default=100)
     ap.add_argument("--probe", action="store_true", help="opt-in variant: visibility query by hash probes of the candidate cells (RE_CFG_PROBE) instead of the key stream")
     ap.add_argument("--pipelined-only", action="store_true", help="profiling aid: only the asynchronous two-lane loop (round 1's headline)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                                                          "(float32 / float64, at most 64 MB; larger outputs as a fixed, seeded sample)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and a.pipelined_only:
+        ap.error("--dump-outputs: the asynchronous frames of --pipelined-only return nothing to the host")
+    return a
 
 
 def world_dims(n_gpus, axis):
@@ -145,6 +157,42 @@ def pin_near_gpu(index):
         return "unchanged (%s)" % str(e)[:80]
 
 
+def _save(out_dir, arrays):
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    for name, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (name, v.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
+def dump_frame(p, vis, tick, out_dir, suffix=""):
+    """--dump-outputs: what one synchronous frame hands its caller -- the counts and InstanceRange table of re_cull_pack, the visible entity
+    ids and model matrices behind them (re_copy_visible) and re_tick's result.  The order of the instances inside a group is not defined
+    (any order, as in the reference), so each group's range is written sorted by entity id.  Beyond DUMP_MAX_INSTANCES
+    visible instances a fixed, seeded sample of the (sorted) rows is written, with its row indices."""
+    ids = np.zeros(vis["n_written"], np.uint32); mats = np.zeros((vis["n_written"], 16), np.float32); nw = C.c_uint32()
+    p._check(p._L.re_copy_visible(p._h, ids.ctypes.data, mats.ctypes.data, vis["n_written"], C.byref(nw)), "re_copy_visible")
+    ids, mats = ids[:nw.value], mats[:nw.value]
+    order = np.arange(len(ids))
+    for g in vis["groups"]:
+        lo, hi = min(int(g["begin"]), len(ids)), min(int(g["begin"]) + int(g["count"]), len(ids))
+        order[lo:hi] = lo + np.argsort(ids[lo:hi], kind="stable")
+    ids, mats = ids[order], mats[order]
+    rows = np.arange(len(ids))
+    if len(ids) > DUMP_MAX_INSTANCES:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(len(ids), DUMP_MAX_INSTANCES, replace=False))
+    g = vis["groups"]
+    _save(out_dir, {
+        "visible_counts" + suffix: np.array([vis["n_visible_sections"], vis["n_visible_vec"], vis["total"], vis["n_written"]], np.float64),
+        "visible_groups" + suffix: np.stack([g[f].astype(np.float64) for f in ("model_index", "render_system", "sortable", "begin", "count")], axis=1).reshape(-1, 5),
+        "visible_rows" + suffix: rows.astype(np.float64),
+        "visible_entity_ids" + suffix: ids[rows].astype(np.float64),
+        "visible_matrices" + suffix: mats[rows],
+        "tick_result" + suffix: np.array([tick["n_changed"], tick["n_rebucket"], tick["n_out_of_bounds"]], np.float64),
+    })
+
+
 def main():
     a = parse()
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1")); local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -168,7 +216,7 @@ def main():
             dist.init_process_group(backend)
     if a.config == "lighting":
         if rank == 0:
-            out = lighting_leg(headline=True, steps=a.steps, warmup=a.warmup)
+            out = lighting_leg(headline=True, steps=a.steps, warmup=a.warmup, dump_dir=a.dump_outputs)
             print(json.dumps(out))
         if dist is not None:
             dist.destroy_process_group()
@@ -221,12 +269,13 @@ def main():
                 exchange = "torch.distributed all_gather_into_tensor (harness; another rank could not set up the communicator)"
 
     def frames(n, record=None):
-        """n synchronous frames; N > 1: the frame ends when the all-gathered visible-instance buffer is complete on this rank"""
+        """n synchronous frames; N > 1: the frame ends when the all-gathered visible-instance buffer is complete on this rank.
+        Returns the last frame's visible set and tick result."""
         if gather is None:
             us, vis, tr = p.run_frames(camc, n, 0.016, cull_flags, tick_flags)        # the two C ABI calls in a native loop
             if record is not None:
                 record.extend(us.tolist())
-            return vis
+            return vis, tr
         cv, ct = F.Visible(), F.TickResult()            # the C ABI straight through ctypes: no per-frame conversion of the results
         for _ in range(n):
             t1 = time.perf_counter()
@@ -237,7 +286,8 @@ def main():
             gather.finish()                             # the gathered buffer is complete on this rank
             if record is not None:
                 record.append((time.perf_counter() - t1) * 1e6)
-        return p._visible_to_py(cv, copy=False) if n else None
+        tr = dict(n_changed=ct.n_changed, n_rebucket=ct.n_rebucket, n_out_of_bounds=ct.n_out_of_bounds)
+        return (p._visible_to_py(cv, copy=False), tr) if n else (None, None)
 
     def fence():
         p.wait()
@@ -265,15 +315,14 @@ def main():
     p.timing_begin(a.steps, every=TIMING_EVERY)
     wall = []
     t_start = time.perf_counter()
-    vis = frames(a.steps, wall)
+    vis, tick = frames(a.steps, wall)
     fence()
     elapsed = time.perf_counter() - t_start
     k1_region = p.timing_collect(a.steps)
     n_cand = p.last_candidates()
-    med_frames = list(wall)
-    if len(med_frames) < MEDIAN_FRAMES:                # median of >= 100 frames
-        frames(MEDIAN_FRAMES - len(med_frames), med_frames)
-        fence()
+    med_frames = list(wall)                            # exactly the K timed frames (SURVEY 8d asks for K >= 100)
+    if a.dump_outputs:                                 # before any further frame overwrites the outputs of the last timed one
+        dump_frame(p, vis, tick, a.dump_outputs, "" if world == 1 else "_rank%d" % rank)
     # the dominant kernel's own launches: at least K1_MIN_LAUNCHES of them whatever --steps was (the timed region alone holds steps / TIMING_EVERY),
     # every launch of further synchronous frames of the same loop, directly behind the timed region
     n_more = max(K1_MIN_LAUNCHES - len(k1_region), 0)
@@ -496,8 +545,9 @@ def spinner_leg(R, a, atomic):
     return out
 
 
-def lighting_leg(headline, steps=20, warmup=3):
-    """configs[4]: deferred lighting of a 4096 x 4096 synthetic G-buffer with 4096 radius ('spot') lights as a HIP compute kernel"""
+def lighting_leg(headline, steps=20, warmup=3, dump_dir=None):
+    """configs[4]: deferred lighting of a 4096 x 4096 synthetic G-buffer with 4096 radius ('spot') lights as a HIP compute kernel.
+    dump_dir: the image of the last timed launch as a fixed, seeded sample of DUMP_PIXELS pixels (lit_pixels, RGBA) and their indices"""
     import oracle as ro
     from render_engine_amd import lighting
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -512,6 +562,9 @@ def lighting_leg(headline, steps=20, warmup=3):
         dl.run()
     us = [dl.run() for _ in range(steps)]
     t = float(np.median(us))
+    if dump_dir:
+        pix = np.sort(np.random.default_rng(DUMP_SEED).choice(W * H, DUMP_PIXELS, replace=False)).astype(np.uint32)
+        _save(dump_dir, {"lit_pixel_index": pix.astype(np.float64), "lit_pixels": dl.read_pixels(pix)})
     keep = []
     S = lighting.fill_lights_struct(ro.LightsC(), L, keep)
     pairs = ro.lighting_spot_pairs(pos, S)             # exact count of (pixel, light within its radius) pairs: the oracle is the counter, not the thing measured

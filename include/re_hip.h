@@ -4,7 +4,7 @@
  * model-matrix pack, and the ECS kinematic / TRS->mat4 tick).
  *
  * Plain pointers and sizes only; no C++/torch types.  A Rust `extern "C"` block binds these 1:1
- * (INTEGRATION.md shows the shim).  Citations are reference file:line under /root/reference/src.
+ * (INTEGRATION.md shows the shim).  Citations are reference file:line under src/ of the reference.
  *
  * The reference has no FFI/plugin layer (one Rust crate, generics + fn pointers), so a per-AABB
  * `TraversalDecider::aabb_in_view` callback (culling/trait.rs:4-7) is the wrong granularity for

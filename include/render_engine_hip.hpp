@@ -3,7 +3,7 @@
 //
 // The reference is one Rust crate without an FFI layer and this image has no Rust toolchain, so the host side above the C
 // ABI is written in C++ with the reference's own names, argument meaning and error behaviour (the Rust shim a maintainer
-// adds is in INTEGRATION.md).  Mirrors, file:line under /root/reference/src:
+// adds is in INTEGRATION.md).  Mirrors, file:line under src/ of the reference:
 //   StaticAABB, XRange/YRange/ZRange        world/bounding_volumes/aabb.rs:7-141, world/dimension/range.rs:7-99
 //   Position .. AccelerationRotation         exports/movement_components.rs:13-164 (axis constructors normalise)
 //   EntityTransformationBuilder              exports/entity_transformer.rs:14-142 (check_invariants asserts -> exceptions)

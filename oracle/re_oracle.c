@@ -2,7 +2,7 @@
  * re_oracle.c -- CPU ORACLE (test infrastructure only; see re_oracle.h header comment).
  *
  * Plain-C restatement of the reference's per-frame visible-set pipeline.  Citations are
- * relative to /root/reference/src.  Compile with -ffp-contract=off -fno-fast-math: Rust never
+ * relative to src/ of the reference.  Compile with -ffp-contract=off -fno-fast-math: Rust never
  * contracts a*b+c into an FMA, and every product/sum below is rounded separately on purpose.
  */
 #define _GNU_SOURCE

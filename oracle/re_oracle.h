@@ -5,7 +5,7 @@
  * and bench.py's cpu_baseline leg may load this library.  The product path
  * (render_engine_amd/, include/re_hip.h) never links, imports or calls it.
  *
- * It is a plain-C restatement of the reference's algorithm (Rust, /root/reference/src);
+ * It is a plain-C restatement of the reference's algorithm (Rust, src/ of the reference);
  * every function cites the reference file:line it follows.  The reference cannot be
  * compiled here (no cargo/rustc, crates un-vendored), so:
  *
@@ -14,7 +14,7 @@
  *     (world/bounding_box_tree_v2.rs:1602-2319, transcribed to tests/golden/tree_cells.json),
  *     UniqueWorldSectionId::to_aabb (:2306-2319), removal sequences (:1837-2217).
  *   - PARITY UNPINNED for everything that goes through nalgebra/nalgebra-glm 0.25.4/0.11.0
- *     (not vendored under /root/reference): frustum planes, corner test, kinematics,
+ *     (not vendored in the reference): frustum planes, corner test, kinematics,
  *     TRS->mat4, AABB transform, distance_to_aabb, LOD.  The reference holds no tests for
  *     those; the formulas below restate nalgebra's published algorithms (operation order
  *     documented per function) and are cross-checked by an independent numpy-float32 mirror

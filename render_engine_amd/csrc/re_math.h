@@ -2,7 +2,7 @@
 // librender_engine_hip.so.  Everything here must round exactly like the reference's Rust/nalgebra
 // code: one IEEE-754 operation per source operation, no FMA contraction (the library is built
 // with -ffp-contract=off), correctly rounded sqrt and division (hipcc default).
-// Citations: reference file:line under /root/reference/src.
+// Citations: reference file:line under src/ of the reference.
 #pragma once
 #include <stdint.h>
 #include <math.h>
