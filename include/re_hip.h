@@ -127,11 +127,11 @@ typedef struct {
                                        * streams, so that the launches of consecutive frames overlap on the GPU (the pack of frame f then rides in launch
                                        * f + 2).  Needs a second copy of the per-frame buffers (~70 B per entity).  re_get_stream returns the stream of the
                                        * frame issued last. */
-#define RE_CULL_FORCE_STREAM    0x8u  /* with RE_CFG_PROBE: take the key stream for this frame anyway */
-#define RE_CULL_ONE_LAUNCH      0x40u /* opt-in, synchronous frames with a small visible set and at most 256 group slots: ONE launch between the call and its answer -- the
-                                      * scan's last workgroup to finish publishes the InstanceRange table and the counts itself (k_scan_cull_sync), the pack launch behind it only
-                                      * moves the instances.  About 1 us less per frame than the two dependent launches; the scan launch then contains the publication chain
-                                      * (DESIGN.md section 4), which is why it is not the default */
+#define RE_CULL_FORCE_STREAM    0x8u  /* take the full key stream for this frame: neither the probe path (RE_CFG_PROBE) nor the chunk plan of a synchronous frame */
+#define RE_CULL_ONE_LAUNCH      0x40u /* synchronous frames with a small visible set and at most 256 group slots: ONE launch between the call and its answer -- the
+                                      * scan's last workgroup to finish publishes the InstanceRange table and the counts itself, the pack launch behind it only moves the
+                                      * instances.  The default whenever the frame's chunk plan is used (k_scan_cull_plan); the flag extends it to
+                                      * frames that stream every key (k_scan_cull_sync) */
 #define RE_CULL_FORCE_LARGE_PACK 0x4u /* always use the multi-kernel pack (count/scan/scatter) instead of k_pack_small */
 
 /* One (ModelId, sortable) group of the packed buffer == ModelRenderingInformation.instance_location
@@ -429,6 +429,9 @@ int re_timing_begin(re_ctx *ctx, uint32_t max_launches, uint32_t every);
 int re_timing_collect(re_ctx *ctx, float *microseconds, uint32_t capacity, uint32_t *n);
 /* number of world sections inside a candidate box in the last cull (== hash probes the reference would make) */
 int re_get_last_candidates(re_ctx *ctx, uint32_t *n_candidates);
+/* frames whose scan read only the key chunks of their chunk plan (synchronous frames with a small visible set), the chunks of the last such plan, and the
+ * chunks written since the last full build that every plan includes (open chunks; 2048 section slots each).  Any pointer may be NULL. */
+int re_debug_get_plan_stats(re_ctx *ctx, uint32_t *n_plan_frames, uint32_t *last_plan_chunks, uint32_t *n_open_chunks);
 /* bytes of DEVICE memory of the ctx (a packed or gathered buffer) into host memory, ordered behind the work on the ctx's stream -- for hosts that hold no HIP
  * runtime of their own, or a different one (a process may carry a second ROCm stack: a pointer of this library means nothing to that one) */
 int re_debug_copy_to_host(re_ctx *ctx, const void *d_src, void *dst, uint64_t bytes);

@@ -87,6 +87,7 @@ extern "C" {
     pub fn re_timing_begin(ctx: *mut ReCtx, max_launches: u32, every: u32) -> c_int;
     pub fn re_timing_collect(ctx: *mut ReCtx, microseconds: *mut f32, capacity: u32, n: *mut u32) -> c_int;
     pub fn re_get_last_candidates(ctx: *mut ReCtx, n_candidates: *mut u32) -> c_int;
+    pub fn re_debug_get_plan_stats(ctx: *mut ReCtx, n_plan_frames: *mut u32, last_plan_chunks: *mut u32, n_open_chunks: *mut u32) -> c_int;
     pub fn re_get_stream(ctx: *mut ReCtx) -> *mut c_void;
     // deferred lighting (BASELINE configs[4]; second pass of RenderSystem::draw)
     pub fn re_lighting_create(cfg: *const ReLightingConfig, out: *mut *mut ReLighting) -> c_int;

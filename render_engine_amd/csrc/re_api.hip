@@ -126,6 +126,12 @@ struct re_ctx {
     std::vector<uint32_t> h_cell_nl, h_cell_ns, h_cell_begin, h_cell_cap, h_rows;   // per slot; h_rows mirrors the row pool
     std::vector<uint64_t> base_keys;                    // slot keys of the last full build (sorted: the lookup base and the span hint)
     std::vector<uint64_t> base_index;                   // every 1024th base key: the cache-resident first level of the lookup
+    // the chunk plan of a synchronous frame (compact keys; chunk_plan): per level, the first slot of every (x, z) column of the last full build
+    // ([x - x0][z - z0], z running to z0 + nz inclusive: the end of column x), and the 2048-key chunks any section was written into since
+    struct PlanLevel { uint32_t x0 = 0, nx = 0, z0 = 0, nz = 0; size_t off = 0; };
+    PlanLevel plan_lv[MAX_LEVELS]; std::vector<uint32_t> plan_first;
+    std::vector<uint32_t> open_chunks; std::vector<uint8_t> open_mark;   // open_chunks ascending
+    uint32_t n_plan_frames = 0, last_plan_chunks = 0, plan_max_chunks = 0, plan_max_open = 0;
     DevBuf<uint8_t> d_stage;                            // staging area of patch uploads
     std::unordered_map<uint64_t, uint32_t> extra_slots;  // sections created since, key -> slot
     std::vector<std::vector<uint32_t>> free_slots;       // per level: padding / emptied slots a new section of that level may take
@@ -271,7 +277,7 @@ namespace {
 struct IssueClock {
     bool on = getenv("RE_EXP_TIME_ISSUE") != nullptr; uint64_t n = 0; double params = 0, spans = 0, scan = 0, pack = 0, wait = 0, finish = 0;
     static double now() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-    void report() const { if (on && n) fprintf(stderr, "host us per frame over %llu frames: parameters %.2f  spans %.2f  scan launch %.2f  pack launch %.2f  wait for the result %.2f  finish %.2f\n",
+    void report() const { if (on && n) fprintf(stderr, "host us per frame over %llu frames: parameters %.2f  spans or chunk plan %.2f  scan launch %.2f  pack launch %.2f  wait for the result %.2f  finish %.2f\n",
                                                  (unsigned long long)n, params / n, spans / n, scan / n, pack / n, wait / n, finish / n); }
 };
 IssueClock g_issue_clock;
@@ -422,6 +428,8 @@ static int ensure_shared_capacity(re_ctx *c, uint32_t need) {
     c->sh_cap = cap; c->rb_sh_dirty = true;
     return RE_OK;
 }
+static void build_plan_table(re_ctx *c);
+static void note_open_slot(re_ctx *c, uint32_t slot);
 static int build_sections(re_ctx *c, const std::vector<uint64_t> &row_key, const std::vector<uint8_t> &row_nk, std::vector<SharedRec> &shrec,
                           const std::vector<uint32_t> &flags, const Carry *carry = nullptr) {
     const uint32_t n = c->n;
@@ -559,7 +567,7 @@ static int build_sections(re_ctx *c, const std::vector<uint64_t> &row_key, const
     // --- upload
     c->ncells = ncells; c->nsh = nsh; c->nrows_csr = (uint32_t)rows.size();
     c->h_cell_key = keys; c->h_row_cell = row_cell; c->h_shids = shids; c->h_sh_nact = sh_nact; c->h_sh_nstat = sh_nstat;
-    c->base_keys = keys; c->extra_slots.clear(); c->base_index.clear(); for (size_t i = 0; i < keys.size(); i += 1024) c->base_index.push_back(keys[i]); c->h_cell_nl = nlocal; c->h_cell_ns = nstatic; c->h_cell_begin.assign(begin.begin(), begin.begin() + ncells);
+    c->base_keys = keys; c->extra_slots.clear(); c->base_index.clear(); for (size_t i = 0; i < keys.size(); i += 1024) c->base_index.push_back(keys[i]); build_plan_table(c); c->h_cell_nl = nlocal; c->h_cell_ns = nstatic; c->h_cell_begin.assign(begin.begin(), begin.begin() + ncells);
     c->h_cell_cap.resize(ncells); for (uint32_t ci = 0; ci < ncells; ci++) c->h_cell_cap[ci] = nlocal[ci] + nstatic[ci] + nghost[ci];
     c->h_cell_ng = nghost;
     c->rb_base_dirty = true; c->rb_ovl_dirty = true; c->stale_slots.clear();      // (a full build is made from the host mirrors, which its callers bring up to date first)
@@ -917,6 +925,91 @@ static void fill_packed_boxes(PBox *out, const LevelBox *in, uint32_t maxlevel) 
         p.min_lo = ok ? ((m1(b.nz) << 16) | m1(b.ny)) : 0u;
         out[l] = p;
     }
+}
+
+// ---- the exact chunk plan of a synchronous frame (k_scan_cull_plan) ------------------------------------------------------------------------------
+// Keys are sorted by (level, x, z, y) at a full build, so the sections of one level and one x with z in [z0, z1] are one contiguous run of slots.
+// The base part of a plan takes those runs for every x of a level's union candidate box; removals since only empty slots inside them.  A section
+// created since sits in a spare or an emptied slot anywhere, outside that order: its chunk is OPEN and every plan scans it, whatever key the slot
+// holds by now.  Every writer of a live key into the table notes its slot here (full build: reset; patch_sections; the device re-bucket's creations).
+constexpr uint32_t PLAN_CHUNK_KEYS = (uint32_t)(CULL_THREADS / 64) * WAVE_KEYS32;      // keys of one workgroup of the scan
+constexpr uint32_t PLAN_OPEN_MAX = 128;                                                  // open chunks beyond this: the frame streams every key until the next full build
+static void build_plan_table(re_ctx *c) {
+    if (!c->plan_max_chunks) {                                                            // (the first build of the ctx)
+        c->plan_max_chunks = PLAN_CHUNKS; c->plan_max_open = PLAN_OPEN_MAX;
+        if (const char *e = getenv("RE_EXP_PLAN_CAPS")) {                                 // (tests: "chunks,open" -- lower caps, so that the fallbacks run)
+            unsigned a = 0, b = 0;
+            if (sscanf(e, "%u,%u", &a, &b) == 2) { c->plan_max_chunks = std::max(1u, std::min(a, PLAN_CHUNKS)); c->plan_max_open = b; }
+        }
+    }
+    for (auto &L : c->plan_lv) L = re_ctx::PlanLevel{};
+    c->plan_first.clear(); c->open_chunks.clear(); c->open_mark.assign(c->base_keys.size() / PLAN_CHUNK_KEYS + 1, 0);
+    if (!c->key32) return;
+    const std::vector<uint64_t> &K = c->base_keys;
+    auto is_pad = [](uint64_t k) { return (k & 0xFFFFFFFFFFFFull) == 0xFFFFFFFFFFFFull; };
+    for (size_t r0 = 0, r1 = 0; r0 < K.size(); r0 = r1) {
+        const uint32_t lv = key_level(K[r0]);
+        uint32_t xmn = 0xFFFFFFFFu, xmx = 0, zmn = 0xFFFFFFFFu, zmx = 0; size_t end = r0;
+        for (r1 = r0; r1 < K.size() && key_level(K[r1]) == lv; r1++)
+            if (!is_pad(K[r1])) { xmn = std::min(xmn, key_x(K[r1])); xmx = std::max(xmx, key_x(K[r1])); zmn = std::min(zmn, key_z(K[r1])); zmx = std::max(zmx, key_z(K[r1])); end = r1 + 1; }
+        if (lv >= (uint32_t)MAX_LEVELS || xmn > xmx) continue;
+        re_ctx::PlanLevel &L = c->plan_lv[lv]; L.x0 = xmn; L.nx = xmx - xmn + 1; L.z0 = zmn; L.nz = zmx - zmn + 1; L.off = c->plan_first.size();
+        const size_t cols = (size_t)L.nz + 1, n = (size_t)L.nx * cols;
+        c->plan_first.resize(L.off + n);
+        uint32_t *T = c->plan_first.data() + L.off; size_t pos = 0;
+        for (size_t i = r0; i < end; i++) {                                   // (pad keys sort behind every real key of their level)
+            const size_t at = (size_t)(key_x(K[i]) - L.x0) * cols + (key_z(K[i]) - L.z0);
+            while (pos <= at) T[pos++] = (uint32_t)i;
+        }
+        while (pos < n) T[pos++] = (uint32_t)end;
+    }
+}
+static void note_open_slot(re_ctx *c, uint32_t slot) {
+    const uint32_t ch = slot / PLAN_CHUNK_KEYS;
+    if (ch >= c->open_mark.size() || c->open_mark[ch]) return;
+    c->open_mark[ch] = 1;
+    c->open_chunks.insert(std::lower_bound(c->open_chunks.begin(), c->open_chunks.end(), ch), ch);
+}
+// The plan: ascending chunks, base part merged with the open chunks.  false: the frame takes the full stream (a candidate box that wraps
+// around the 16-bit index space, more open chunks or more chunks than a plan holds, no table).
+static bool chunk_plan(re_ctx *c, ScanPlan &Q, uint32_t *nplan) {
+    if (!c->key32 || c->plan_first.empty() || c->open_chunks.size() > c->plan_max_open) return false;
+    const FrameParams &P = c->P;
+    uint32_t base[PLAN_CHUNKS], nb = 0;
+    for (uint32_t l = 0; l < P.max_level && l < (uint32_t)MAX_LEVELS; l++) {
+        uint32_t x0 = 0xFFFFFFFFu, x1 = 0, z0 = 0xFFFFFFFFu, z1 = 0;             // the union of the two candidate boxes in x and z, [x0, x1) x [z0, z1)
+        for (int w = 0; w < 2; w++) {
+            const LevelBox &b = P.box[w][l];
+            if (!b.nx || !b.ny || !b.nz) continue;
+            if (b.bx + b.nx > 0xFFFFu || b.bz + b.nz > 0xFFFFu) return false;   // wraps (or starts beyond 0xFFFF)
+            x0 = std::min(x0, b.bx); x1 = std::max(x1, b.bx + b.nx); z0 = std::min(z0, b.bz); z1 = std::max(z1, b.bz + b.nz);
+        }
+        const re_ctx::PlanLevel &L = c->plan_lv[l];
+        if (x0 >= x1 || !L.nx) continue;
+        const uint32_t xa = std::max(x0, L.x0), xb = std::min(x1, L.x0 + L.nx), za = std::max(z0, L.z0), zb = std::min(z1, L.z0 + L.nz);
+        if (xa >= xb || za >= zb) continue;
+        const uint32_t *T = c->plan_first.data() + L.off; const size_t cols = (size_t)L.nz + 1;
+        for (uint32_t x = xa; x < xb; x++) {
+            const uint32_t s0 = T[(x - L.x0) * cols + (za - L.z0)], s1 = T[(x - L.x0) * cols + (zb - L.z0)];
+            if (s0 >= s1) continue;
+            for (uint32_t ch = s0 / PLAN_CHUNK_KEYS; ch <= (s1 - 1u) / PLAN_CHUNK_KEYS; ch++) {     // slots ascend with (level, x): duplicates only at the seams
+                if (nb && base[nb - 1] >= ch) continue;
+                if (nb == c->plan_max_chunks) return false;
+                base[nb++] = ch;
+            }
+        }
+    }
+    const uint32_t *o = c->open_chunks.data(); const size_t no = c->open_chunks.size();
+    uint32_t n = 0; size_t i = 0, j = 0;
+    while (i < nb || j < no) {
+        const uint32_t ch = (j == no || (i < nb && base[i] <= o[j])) ? base[i] : o[j];
+        if (i < nb && base[i] == ch) i++;
+        if (j < no && o[j] == ch) j++;
+        if (n == c->plan_max_chunks) return false;
+        Q.chunk[n++] = ch;
+    }
+    *nplan = n;
+    return true;
 }
 
 // Key chunks (2048 keys = one workgroup of k_scan_cull) that can hold candidates: per level, the x-slab [bx, bx+nx) of the union of
@@ -1315,18 +1408,36 @@ static int issue_cull(re_ctx *c, const re_camera *cam, uint32_t flags) {
         }
     }
     lap(IC.params);
-    const ScanSpans SP = probed ? ScanSpans{} : candidate_spans(c, scan_grid);
-    lap(IC.spans);
     // a pack deferred by the previous frame rides in the first workgroups of this frame's scan (one launch per frame); any other
     // kind of launch here sends it off on its own first
     const bool fuse = c->deferred_pack && !probed && c->deferred_grid < (1u << 20);
+    // a synchronous frame with a small visible set scans only the chunks of its plan (k_scan_cull_plan), and by default that launch's last
+    // workgroup publishes the result (RE_EXP_PLAN_TWO_LAUNCH: k_pack_small publishes, as behind the full stream)
+    ScanPlan Q; uint32_t nplan = 0;
+    const bool planned = small && !(flags & (RE_CULL_ASYNC | RE_CULL_FORCE_STREAM)) && !probed && !fuse && !count_in_scan && chunk_plan(c, Q, &nplan);
+    const ScanSpans SP = (probed || planned) ? ScanSpans{} : candidate_spans(c, scan_grid);
+    lap(IC.spans);
     if (c->deferred_pack && !fuse) { int rc = flush_deferred_pack(c); if (rc != RE_OK) return rc; }
     const size_t fused_lds = (size_t)std::max(c->nslots, 1u) * 8;
-    // a synchronous frame with a small visible set: the scan's last workgroup publishes the result itself (k_scan_cull_sync), the pack launch behind it only moves the instances
+    // a synchronous frame with a small visible set: the scan's last workgroup publishes the result itself (k_scan_cull_sync / k_scan_cull_plan<true>), the pack launch
+    // behind it only moves the instances
     static const bool always_one = getenv("RE_EXP_ONE_LAUNCH_SYNC") != nullptr;       // (testing: every eligible synchronous frame of the process)
-    const bool one_launch = ((flags & RE_CULL_ONE_LAUNCH) || always_one) && small && !(flags & RE_CULL_ASYNC) && !probed && !fuse && !count_in_scan && c->nslots <= SYNC_TAIL_SLOTS;
+    static const bool plan_two = getenv("RE_EXP_PLAN_TWO_LAUNCH") != nullptr;         // (A/B: the compact scan + a publishing k_pack_small)
+    const bool sync_ok = small && !(flags & RE_CULL_ASYNC) && !probed && !fuse && !count_in_scan && c->nslots <= SYNC_TAIL_SLOTS;
+    const bool one_launch = sync_ok && (planned ? !plan_two : ((flags & RE_CULL_ONE_LAUNCH) || always_one));
     if (one_launch) SA.K.slot_write_through = 1u;
-    if (probed) {}
+    if (planned) {
+        // the first workgroups also cull the shared sections (as k_probe_cull's grid); the last one stages the frame parameters and, publishing, the result
+        const uint32_t grid = std::max(std::max(nplan, 1u), std::min((c->nsh + CULL_THREADS - 1) / CULL_THREADS, 2048u));
+        if (one_launch)
+            hipExtLaunchKernelGGL(k_scan_cull_plan<true>, dim3(grid), dim3(CULL_THREADS), (size_t)std::max(c->nslots, 1u) * 4, st, k1a, k1b, 0, (const void *)c->d_cell_key32.p, c->ncells, nplan,
+                                  0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, (const uint32_t *)c->d_chunk_level.p, SA, A, Q);
+        else
+            hipExtLaunchKernelGGL(k_scan_cull_plan<false>, dim3(grid), dim3(CULL_THREADS), scan_lds, st, k1a, k1b, 0, (const void *)c->d_cell_key32.p, c->ncells, nplan,
+                                  0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, (const uint32_t *)c->d_chunk_level.p, SA, A, Q);
+        c->n_plan_frames++; c->last_plan_chunks = nplan;
+    }
+    else if (probed) {}
     else if (one_launch && c->key32)
         hipExtLaunchKernelGGL(k_scan_cull_sync<true>, dim3(scan_grid), dim3(CULL_THREADS), (size_t)std::max(c->nslots, 1u) * 4, st, k1a, k1b, 0, (const void *)c->d_cell_key32.p, c->ncells, SP.n, SP.start[0], SP.count[0],
                               SP.start[1], SP.count[1], SP.start[2], SP.count[2], SP.start[3], SP.count[3], (const uint32_t *)c->d_chunk_level.p, SA, A);
@@ -1530,7 +1641,7 @@ static int patch_sections(re_ctx *c, const Carry &carry, const std::map<uint64_t
             const uint32_t lv = key_level(K) & (MAX_LEVELS - 1);
             if (c->free_slots[lv].empty()) return c->fail(RE_E_STATE, "patch_sections: free-slot accounting");
             slot = (int32_t)c->free_slots[lv].back(); c->free_slots[lv].pop_back(); slot_memo[K] = slot;
-            c->h_cell_key[slot] = K; c->extra_slots[K] = (uint32_t)slot; c->h_cell_cap[slot] = 0; c->h_cell_begin[slot] = 0; p_cap.push_back(Pair32{ (uint32_t)slot, 0u });
+            c->h_cell_key[slot] = K; c->extra_slots[K] = (uint32_t)slot; note_open_slot(c, (uint32_t)slot); c->h_cell_cap[slot] = 0; c->h_cell_begin[slot] = 0; p_cap.push_back(Pair32{ (uint32_t)slot, 0u });
             p_key.push_back(Pair64{ (uint32_t)slot, 0, K }); p_stamp.push_back(Pair32{ (uint32_t)slot, 0 });
             FlagOp &f = fop((uint32_t)slot); f.and_mask = 0; f.or_mask = 0;
             if (c->dormant_cached.erase(K)) f.or_mask |= CF_STATIC_CACHED;          // its cache entry (now ghosts only) is reachable again
@@ -2099,7 +2210,7 @@ static int rebucket_on_device2(re_ctx *c, uint32_t M, std::vector<uint32_t> *hos
         if (G.slot < 0) continue;
         c->stale_slots.push_back((uint32_t)G.slot);
         if (G.freed) { c->free_slots[key_level(G.key) & (MAX_LEVELS - 1)].push_back((uint32_t)G.slot); delta--; }
-        if (G.created) delta++;
+        if (G.created) { delta++; note_open_slot(c, (uint32_t)G.slot); }
     }
     for (uint32_t i2 = 0; i2 < ns; i2++) { const Rb2ShSeg &G = ss[i2];
         if (G.idx < 0) continue;
@@ -3691,6 +3802,14 @@ extern "C" int re_debug_get_shared_sections(re_ctx *c, uint32_t capacity, uint64
     }
     return RE_OK;
 } RE_ABI_GUARD(c, "re_debug_get_shared_sections")
+
+extern "C" int re_debug_get_plan_stats(re_ctx *c, uint32_t *n_plan_frames, uint32_t *last_plan_chunks, uint32_t *n_open_chunks) try {
+    if (!c) return RE_E_ARG;
+    if (n_plan_frames) *n_plan_frames = c->n_plan_frames;
+    if (last_plan_chunks) *last_plan_chunks = c->last_plan_chunks;
+    if (n_open_chunks) *n_open_chunks = (uint32_t)c->open_chunks.size();
+    return RE_OK;
+} RE_ABI_GUARD(c, "re_debug_get_plan_stats")
 
 extern "C" int re_debug_get_visible_sections(re_ctx *c, uint32_t capacity, uint64_t *keys, uint8_t *multiplicity, uint32_t *n) try {
     if (!c || !c->have_cull) return RE_E_ARG;

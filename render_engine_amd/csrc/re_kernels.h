@@ -182,6 +182,15 @@ template <bool K32> __global__ void k_scan_cull_sync(const void *keys, uint32_t 
                                                      uint32_t s3, uint32_t c3, const uint32_t *chunk_level, ScanCullArgs A, PackArgs T);
 extern template __global__ void k_scan_cull_sync<false>(const void *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, const uint32_t *, ScanCullArgs, PackArgs);
 extern template __global__ void k_scan_cull_sync<true>(const void *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, const uint32_t *, ScanCullArgs, PackArgs);
+// The compact scan of a synchronous frame with a small visible set: the grid is the frame's chunk plan (every key chunk that can hold a
+// candidate, built on the host: chunk_plan in re_api.hip) instead of every chunk of the table.  nsp carries the plan's length; workgroups
+// beyond it only cull shared sections and sign off.  SYNC: the last workgroup publishes the frame as in k_scan_cull_sync.
+constexpr uint32_t PLAN_CHUNKS = 256;          // 2048-key chunks a plan may hold (1 KB of kernel arguments)
+struct ScanPlan { uint32_t chunk[PLAN_CHUNKS]; };   // ascending chunk indices
+template <bool SYNC> __global__ void k_scan_cull_plan(const void *keys, uint32_t ncells, uint32_t nplan, uint32_t s0, uint32_t c0, uint32_t s1, uint32_t c1, uint32_t s2, uint32_t c2,
+                                                      uint32_t s3, uint32_t c3, const uint32_t *chunk_level, ScanCullArgs A, PackArgs T, ScanPlan Q);
+extern template __global__ void k_scan_cull_plan<false>(const void *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, const uint32_t *, ScanCullArgs, PackArgs, ScanPlan);
+extern template __global__ void k_scan_cull_plan<true>(const void *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, const uint32_t *, ScanCullArgs, PackArgs, ScanPlan);
 struct FusedPack { FrameHeader *hdr, *hdr_next; TickHeader *th; PackArgs A; ItemSink K; uint32_t nrows, pad; };   // the previous frame's pack, carried by the next frame's launch
 template <bool K32> __global__ void k_scan_cull_fused(const void *keys, uint32_t ncells, uint32_t nsp_npack, uint32_t s0, uint32_t c0, uint32_t s1, uint32_t c1, uint32_t s2, uint32_t c2,
                                                       uint32_t s3, uint32_t c3, const uint32_t *chunk_level, ScanCullArgs A, FusedPack F);

@@ -300,7 +300,10 @@ __device__ __forceinline__ void cull_shared_section(uint32_t s, const SharedArra
 // The body of the scan + cull kernel for workgroup `bid` of `nblk` (the kernel's own grid, or the scan part of the fused launch below).
 // Force-inlined into its kernels: `A` is the kernel's by-value argument, and the kernel-argument offsets used below are those of the
 // common leading signature.
-template <bool K32, bool EAGER = false>
+constexpr uint32_t SYNC_TAIL_ARGS_OFFSET = SCAN_CULL_ARGS_OFFSET + (uint32_t)((sizeof(ScanCullArgs) + 7u) & ~(size_t)7u);   // PackArgs of k_scan_cull_sync / k_scan_cull_plan
+constexpr uint32_t PLAN_ARGS_OFFSET = SYNC_TAIL_ARGS_OFFSET + (uint32_t)((sizeof(PackArgs) + 7u) & ~(size_t)7u);               // ScanPlan of k_scan_cull_plan
+// PLAN (k_scan_cull_plan): workgroup bid < nsp scans chunk ScanPlan::chunk[bid] (one scalar load); the workgroups behind the plan scan nothing
+template <bool K32, bool EAGER = false, bool PLAN = false>
 __device__ __forceinline__ void scan_cull_body(const uint32_t bid, const uint32_t nblk, const void *__restrict__ keys, uint32_t ncells, uint32_t nsp, uint32_t s0, uint32_t c0, uint32_t s1, uint32_t c1,
                                                uint32_t s2, uint32_t c2, uint32_t s3, uint32_t c3, const uint32_t *__restrict__ chunk_level, const ScanCullArgs &A) {
     constexpr uint32_t WK = WAVE_KEYS, NB = WK / 64u, NLD = K32 ? 2u : CULL_ITERS;   // keys per wave; ballots per wave (one per key a lane holds); 16-byte loads per lane
@@ -311,8 +314,13 @@ __device__ __forceinline__ void scan_cull_body(const uint32_t bid, const uint32_
     const unsigned long long tl_start = wall_clock64(); unsigned long long tl_keys = tl_start, tl_pred = 0, tl_emit = 0; uint32_t tl_cand = 0;
 #endif
     // workgroup -> key chunk: the candidate spans first (see ScanSpans); all scalar
-    uint32_t chunk = bid;
-    {
+    uint32_t chunk = bid; bool live = true;
+    if constexpr (PLAN) {
+        typedef __attribute__((address_space(4))) const char *kernarg_ptr;
+        const ScanPlan &Q = *(const ScanPlan *)((kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr() + PLAN_ARGS_OFFSET);
+        live = bid < nsp;
+        chunk = Q.chunk[live ? bid : 0u];
+    } else {
         const uint32_t st[4] = { s0, s1, s2, s3 }, ct[4] = { c0, c1, c2, c3 };
         uint32_t acc = 0; bool in_span = false;
 #pragma unroll
@@ -327,7 +335,7 @@ __device__ __forceinline__ void scan_cull_body(const uint32_t bid, const uint32_
     const uint32_t lane = lane_id(), wid = threadIdx.x >> 6, wave = chunk * (CULL_THREADS / 64) + wid;
     // the stream: 512 keys per wave, as 4 x 16 B (full 64-bit keys) or 2 x 16 B (compact 32-bit keys) per lane; one ballot per key a lane holds
     const uint32_t wave_key0 = wave * WK;
-    if (wave_key0 < ncells) {                                               // wave-uniform
+    if (live && wave_key0 < ncells) {                                       // wave-uniform
         uint64_t m[NB]; uint64_t any = 0; uint32_t lv0, qn = 0;
         uint32_t *q_idx = s_idx[wid], *q_key = s_key[wid];
         if constexpr (K32) {
@@ -521,7 +529,7 @@ __device__ __forceinline__ void scan_cull_body(const uint32_t bid, const uint32_
             for (uint32_t i = threadIdx.x; i < sizeof(FrameParams) / 4u; i += CULL_THREADS) dst[i] = src[i];
         }
 #ifdef RE_EXP_STAMPS
-        if (R.timeline && lane == 0) { unsigned long long *t = R.timeline + (size_t)wave * 8u; t[0] = tl_start; t[1] = tl_keys; t[2] = wall_clock64(); t[3] = tl_cand; t[4] = tl_pred; t[5] = tl_emit; }
+        if (R.timeline && live && lane == 0) { unsigned long long *t = R.timeline + (size_t)wave * 8u; t[0] = tl_start; t[1] = tl_keys; t[2] = wall_clock64(); t[3] = tl_cand; t[4] = tl_pred; t[5] = tl_emit; }
 #endif
     }
 }
@@ -1264,7 +1272,6 @@ template __global__ void k_scan_cull_fused<true>(const void *, uint32_t, uint32_
 // was written by atomics or write-through stores of this same launch), the histogram in LDS, the InstanceRange table and the result block straight into
 // mapped host memory (publish_to_host).  k_pack_small follows on the stream with PACK_NO_PUBLISH and moves the instances while the host is already back.
 // ---------------------------------------------------------------------------------------------
-constexpr uint32_t SYNC_TAIL_ARGS_OFFSET = SCAN_CULL_ARGS_OFFSET + (uint32_t)((sizeof(ScanCullArgs) + 7u) & ~(size_t)7u);
 __device__ __forceinline__ uint32_t load_agent(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void sync_frame_publish(FrameHeader *hdr, const ItemSink &K, const PackArgs &A) {          // ONE wave
     extern __shared__ uint32_t s_dyn[];                       // [nslots]: instances per group slot
@@ -1333,13 +1340,12 @@ __device__ __forceinline__ void sync_frame_publish(FrameHeader *hdr, const ItemS
         publish_to_host(&A.hres->done_frame, A.frame);
     }
 }
-template <bool K32>
-__global__ __launch_bounds__(CULL_THREADS) void k_scan_cull_sync(const void *__restrict__ keys, uint32_t ncells, uint32_t nsp, uint32_t s0, uint32_t c0, uint32_t s1, uint32_t c1,
-                                                                 uint32_t s2, uint32_t c2, uint32_t s3, uint32_t c3, const uint32_t *__restrict__ chunk_level, ScanCullArgs A, PackArgs T) {
-    scan_cull_body<K32>(blockIdx.x, gridDim.x, keys, ncells, nsp, s0, c0, s1, c1, s2, c2, s3, c3, chunk_level, A);
+// the tail of a publishing scan launch, after scan_cull_body: every workgroup signs off on the sharded ticket, the last one publishes the frame
+__device__ __forceinline__ void sync_sign_off() {
     wait_own_stores();                                        // this wave's list entries (write-through) and atomics have been performed ...
     __syncthreads();                                          // ... before the workgroup signs off
     if (threadIdx.x >= 64u) return;
+
     typedef __attribute__((address_space(4))) const char *kernarg_ptr;
     kernarg_ptr ka = (kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(ka));                              // (as in the body: none of these scalar loads in front of the key loads)
@@ -1357,8 +1363,24 @@ __global__ __launch_bounds__(CULL_THREADS) void k_scan_cull_sync(const void *__r
     const PackArgs &P2 = *(const PackArgs *)(ka + SYNC_TAIL_ARGS_OFFSET);
     sync_frame_publish(hdr, R.K, P2);
 }
+template <bool K32>
+__global__ __launch_bounds__(CULL_THREADS) void k_scan_cull_sync(const void *__restrict__ keys, uint32_t ncells, uint32_t nsp, uint32_t s0, uint32_t c0, uint32_t s1, uint32_t c1,
+                                                                 uint32_t s2, uint32_t c2, uint32_t s3, uint32_t c3, const uint32_t *__restrict__ chunk_level, ScanCullArgs A, PackArgs T) {
+    scan_cull_body<K32>(blockIdx.x, gridDim.x, keys, ncells, nsp, s0, c0, s1, c1, s2, c2, s3, c3, chunk_level, A);
+    sync_sign_off();
+}
 template __global__ void k_scan_cull_sync<false>(const void *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, const uint32_t *, ScanCullArgs, PackArgs);
 template __global__ void k_scan_cull_sync<true>(const void *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, const uint32_t *, ScanCullArgs, PackArgs);
+// the compact scan (compact keys only): the grid is the frame's chunk plan; SYNC: its last workgroup publishes the frame (the default of a synchronous
+// frame with a small visible set); otherwise k_pack_small behind it publishes, as behind k_scan_cull
+template <bool SYNC>
+__global__ __launch_bounds__(CULL_THREADS) void k_scan_cull_plan(const void *__restrict__ keys, uint32_t ncells, uint32_t nplan, uint32_t s0, uint32_t c0, uint32_t s1, uint32_t c1,
+                                                                 uint32_t s2, uint32_t c2, uint32_t s3, uint32_t c3, const uint32_t *__restrict__ chunk_level, ScanCullArgs A, PackArgs T, ScanPlan Q) {
+    scan_cull_body<true, false, true>(blockIdx.x, gridDim.x, keys, ncells, nplan, s0, c0, s1, c1, s2, c2, s3, c3, chunk_level, A);
+    if constexpr (SYNC) sync_sign_off();
+}
+template __global__ void k_scan_cull_plan<false>(const void *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, const uint32_t *, ScanCullArgs, PackArgs, ScanPlan);
+template __global__ void k_scan_cull_plan<true>(const void *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, const uint32_t *, ScanCullArgs, PackArgs, ScanPlan);
 
 // ---------------------------------------------------------------------------------------------
 // K3: the ECS tick.  LogicFlow::apply_kinematics (flows/logic_flow.rs:366-448) + the component math of
