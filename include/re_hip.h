@@ -183,6 +183,7 @@ typedef struct {
 #define RE_C_STATIC_AABB     8   /* 6 floats */
 #define RE_C_ORIGINAL_AABB   9   /* 6 floats */
 #define RE_C_FLAGS          10   /* 1 uint32: RE_F_* incl. HasMoved/HasRotated */
+#define RE_C_LIGHT_INFORMATION 11 /* re_light_information (80 bytes); RE_E_ARG when the entity does not carry it */
 
 /* ---- lifecycle ---- */
 int         re_create(const re_config *cfg, re_ctx **out);
@@ -364,6 +365,7 @@ int re_read_component(re_ctx *ctx, uint32_t entity_id, int component, void *dst)
 #define RE_ECS_BIT_MODEL_ID             13
 #define RE_ECS_BIT_STATIC_AABB          15
 #define RE_ECS_BIT_ORIGINAL_AABB        16
+#define RE_ECS_BIT_LIGHT_INFORMATION    19  /* set by re_set_light_information */
 #define RE_ECS_BIT_ALWAYS_EXECUTE_LOGIC 20
 int re_ecs_bitset(re_ctx *ctx, uint32_t entity_id, uint32_t *bits);   /* 0 for an entity that was removed (remove_entity clears every bit, ecs.rs:557-600) */
 /* Sharding helper: the world sections entity i is registered in -- n_keys[i] = 1 (its unique section) or 2..8 (the sections its shared
@@ -379,6 +381,21 @@ int re_section_keys(const re_config *cfg, const re_entities *entities, uint64_t 
  * of the shared sections linked to them).  light_type: one of RE_F_LIGHT_DIRECTIONAL / RE_F_LIGHT_POINT / RE_F_LIGHT_SPOT.  *n = number found (may exceed
  * capacity); ids in ascending order.  Independent of re_cull_pack (it runs its own visibility test), after the movers of the last tick are in. */
 int re_visible_lights(re_ctx *ctx, const re_camera *cam, uint32_t light_type, uint32_t *ids, uint32_t capacity, uint32_t *n);
+
+/* LightInformation (exports/light_components.rs:11-24), ECS component bit 19 (flows/logic_flow.rs:83-110): what upload_*_lights reads of a light besides
+ * its Position.  present: one RE_LI_* bit per Option field that is Some; the fields of a bit that is clear are ignored. */
+#define RE_LI_CUTOFF        1u
+#define RE_LI_OUTER_CUTOFF  2u
+#define RE_LI_DIRECTION     4u
+#define RE_LI_FOV           8u
+typedef struct re_light_information {
+    float radius, diffuse[3], specular[3], ambient[4], linear, quadratic, cutoff, outer_cutoff, direction[3], fov;
+    uint32_t present;
+} re_light_information;   /* 80 bytes */
+/* ECS::write_component::<LightInformation> for n entities (info[i] for entity_ids[i]); info == NULL removes the component.  Any live entity may carry it;
+ * an unknown or removed id refuses the whole batch (RE_E_ARG).  The component goes away with the entity (delete, leaving the world) and on
+ * re_upload_entities; a reused id starts without it.  Read back with re_read_component(RE_C_LIGHT_INFORMATION). */
+int re_set_light_information(re_ctx *ctx, const uint32_t *entity_ids, uint32_t n, const re_light_information *info);
 
 /* ECS::get_indexes_for_components (objects/ecs.rs:238-285): the entities that carry ALL the given components (RE_C_*), in ascending EntityId (the
  * reference returns a BTreeSet).  *n = their number; the first `capacity` ids are written.  Runs on the GPU over the presence column. */
@@ -468,6 +485,28 @@ int re_lighting_set_lights(re_lighting *l, const re_lights *lights);
 int re_lighting_run(re_lighting *l, float *kernel_microseconds /* nullable */);      /* FragColor RGBA32F stays in HBM */
 int re_lighting_read(re_lighting *l, float *out_rgba);                                 /* width*height*4 floats */
 int re_lighting_read_pixels(re_lighting *l, const uint32_t *pixel_index, uint32_t n, float *out_rgba);
+/* The three upload_*_lights calls of one render system's draw (render_system/render_system.rs:563-576, 681-845), fed from the world of ctx without a host
+ * round trip: per type the lights re_visible_lights(cam, type) finds ("nearby", ascending EntityId); when none, the type's arrays stay as they were;
+ * otherwise the slots are previous ∩ nearby followed by nearby, the first min(|nearby|, max) of them (a light can take two slots), and they become the
+ * type's previous set.  The previous sets live in the lighting context (one context = one render system's second pass).  Positions are the live ones
+ * (ordered behind the work already enqueued on ctx's stream), the rest comes from the lights' LightInformation.  Spot ("radius") lights fill all
+ * max_spot_lights slots, the ones past the selection with zeros (numberSpotLights = max_spot_lights).  re_lighting_run then renders with them.
+ * out (nullable) receives the counts and the slot ids (host memory owned by the library until the next call); with out == NULL the call does not wait
+ * for the device unless some light of a type lacks what that type unwraps.
+ * Errors: ctx and l on different devices (RE_E_ARG), no world uploaded (RE_E_STATE), a ctx with a shard range (RE_E_UNSUPPORTED: a shard sees only its
+ * own lights), a selected light without LightInformation or without a field its type unwraps -- direction for directional lights, cutoff, outer
+ * cutoff, direction and fov for point lights -- (RE_E_STATE, naming the entity; the lighting context and the previous sets are left unchanged). */
+#define RE_WL_DIRECTIONAL 0
+#define RE_WL_POINT       1
+#define RE_WL_SPOT        2
+typedef struct { uint32_t max_directional_lights; float no_light_source_cutoff, default_diffuse_factor; } re_world_light_args;
+typedef struct {
+    uint32_t any_light_source_visible;
+    uint32_t n_nearby[3];                /* [RE_WL_*] */
+    uint32_t n_slots[3];                 /* 0: the type's arrays were left as they were */
+    const uint32_t *slot_ids[3];         /* n_slots[t] entity ids in slot order, duplicates included */
+} re_world_lights;
+int re_lighting_set_lights_from_world(re_lighting *l, re_ctx *ctx, const re_camera *cam, const re_world_light_args *args, re_world_lights *out /* nullable */);
 
 /* ---- history / replay wire format ----
  * The per-frame FrameChange records of the history thread (threads/public_common_structures.rs:7-16), written with bincode 1.3 as

@@ -318,6 +318,21 @@ class Pipeline {
         if (n) check(re_visible_lights(ctx_, &cam, flag, ids.data(), n, &n), "re_visible_lights");
         return ids;
     }
+    // ECS::write_component::<LightInformation> (exports/light_components.rs:11-24) / get_ref::<LightInformation>
+    void write_light_information(EntityId e, const re_light_information &info) { upload_if_needed(); check(re_set_light_information(ctx_, &e, 1u, &info), "re_set_light_information"); }
+    void remove_light_information(EntityId e) { upload_if_needed(); check(re_set_light_information(ctx_, &e, 1u, nullptr), "re_set_light_information"); }
+    re_light_information get_light_information(EntityId e) { re_light_information v{}; read(e, RE_C_LIGHT_INFORMATION, &v); return v; }
+    // RenderSystem::draw's upload_{directional,point,spot}_lights (render_system/render_system.rs:563-576, 681-845) into one render system's lighting context
+    // (which keeps that render system's previous sets); out (nullable) receives the slot ids per type and anyLightSourceVisible
+    void upload_lights(re_lighting *lighting, const Camera &camera, uint32_t max_directional_lights, float no_light_source_cutoff, float default_diffuse_factor,
+                       re_world_lights *out = nullptr) {
+        upload_if_needed();
+        re_camera cam{}; const TVec3 cp = camera.get_position();
+        cam.position[0] = cp.x; cam.position[1] = cp.y; cam.position[2] = cp.z; cam.far_draw = camera.get_far_draw_distance();
+        const re_world_light_args args{ max_directional_lights, no_light_source_cutoff, default_diffuse_factor };
+        const int rc = re_lighting_set_lights_from_world(lighting, ctx_, &cam, &args, out);
+        if (rc != RE_OK) throw std::runtime_error(std::string("re_lighting_set_lights_from_world: ") + re_lighting_last_error(lighting));
+    }
     // RenderFlow::register_model_with_render_system with custom_level_of_view (flows/render_flow.rs:1069-1076)
     void register_custom_level_of_view(ModelId model_id, const std::vector<float> &min_distance, const std::vector<float> &max_distance) {
         check(re_set_model_lod(ctx_, model_id.model_index, model_id.render_system_index, (uint32_t)std::min(min_distance.size(), max_distance.size()), min_distance.data(), max_distance.data()), "re_set_model_lod");

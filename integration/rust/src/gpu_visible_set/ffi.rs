@@ -35,6 +35,10 @@ use std::os::raw::{c_char, c_int, c_void};
     pub point_pos: *const f32, pub point_dir: *const f32, pub point_diffuse: *const f32, pub point_specular: *const f32, pub point_ambient: *const f32, pub point_linear: *const f32,
     pub point_quadratic: *const f32, pub point_cutoff: *const f32, pub point_outer_cutoff: *const f32,
     pub camera_pos: [f32; 3], pub no_light_source_cutoff: f32, pub default_diffuse_factor: f32, pub any_light_source_visible: u32 }
+#[repr(C)] #[derive(Copy, Clone, Default)] pub struct ReLightInformation { pub radius: f32, pub diffuse: [f32; 3], pub specular: [f32; 3], pub ambient: [f32; 4], pub linear: f32,
+    pub quadratic: f32, pub cutoff: f32, pub outer_cutoff: f32, pub direction: [f32; 3], pub fov: f32, pub present: u32 }   // 80 bytes
+#[repr(C)] pub struct ReWorldLightArgs { pub max_directional_lights: u32, pub no_light_source_cutoff: f32, pub default_diffuse_factor: f32 }
+#[repr(C)] pub struct ReWorldLights { pub any_light_source_visible: u32, pub n_nearby: [u32; 3], pub n_slots: [u32; 3], pub slot_ids: [*const u32; 3] }
 #[repr(C)] pub struct ReHistory { _private: [u8; 0] }
 #[repr(C)] pub struct ReTypeIds { pub position: u64, pub rotation: u64, pub scale: u64, pub velocity: u64, pub acceleration: u64, pub rotation_velocity: u64,
                                   pub rotation_acceleration: u64, pub has_moved: u64, pub has_rotated: u64 }
@@ -63,6 +67,7 @@ extern "C" {
     pub fn re_ecs_bitset(ctx: *mut ReCtx, entity_id: u32, bits: *mut u32) -> c_int;
     pub fn re_ecs_query(ctx: *mut ReCtx, components: *const c_int, n_components: u32, ids: *mut u32, capacity: u32, n: *mut u32) -> c_int;
     pub fn re_visible_lights(ctx: *mut ReCtx, cam: *const ReCamera, light_type: u32, ids: *mut u32, capacity: u32, n: *mut u32) -> c_int;
+    pub fn re_set_light_information(ctx: *mut ReCtx, entity_ids: *const u32, n: u32, info: *const ReLightInformation) -> c_int;
     pub fn re_section_keys(cfg: *const ReConfig, ents: *const ReEntities, keys: *mut u64 /* [n * 8] */, n_keys: *mut u8 /* [n] */) -> c_int;   // host arithmetic: the sharding key of a multi-GPU loader
     pub fn re_comm_unique_id(id: *mut u8) -> c_int;                                                            // RE_COMM_ID_BYTES = 128
     pub fn re_comm_init(ctx: *mut ReCtx, id: *const u8, rank: c_int, n_ranks: c_int, slab_instances: u32) -> c_int;
@@ -98,6 +103,7 @@ extern "C" {
     pub fn re_lighting_run(l: *mut ReLighting, kernel_microseconds: *mut f32) -> c_int;
     pub fn re_lighting_read(l: *mut ReLighting, out_rgba: *mut f32) -> c_int;
     pub fn re_lighting_read_pixels(l: *mut ReLighting, pixel_index: *const u32, n: u32, out_rgba: *mut f32) -> c_int;
+    pub fn re_lighting_set_lights_from_world(l: *mut ReLighting, ctx: *mut ReCtx, cam: *const ReCamera, args: *const ReWorldLightArgs, out: *mut ReWorldLights) -> c_int;
     pub fn re_history_create(ids: *const ReTypeIds, flags: u32, out: *mut *mut ReHistory) -> c_int;
     pub fn re_history_destroy(h: *mut ReHistory);
     pub fn re_history_last_error(h: *const ReHistory) -> *const c_char;
@@ -126,3 +132,6 @@ pub const RE_FC_CAMERA_VIEW_CHANGE: u32 = 0; pub const RE_FC_CAMERA_STATIONARY: 
 pub const RE_FC_WINDOW_DIMENSIONS_CHANGE: u32 = 4; pub const RE_FC_ENTITY_CHANGE: u32 = 5; pub const RE_FC_END_FRAME_CHANGE: u32 = 6;
 pub const RE_F_LIGHT_DIRECTIONAL: u32 = 0x2000; pub const RE_F_LIGHT_POINT: u32 = 0x4000; pub const RE_F_LIGHT_SPOT: u32 = 0x8000;
 pub const RE_F_PHANTOM: u32 = 0x10000;
+pub const RE_C_LIGHT_INFORMATION: u32 = 11; pub const RE_ECS_BIT_LIGHT_INFORMATION: u32 = 19;
+pub const RE_LI_CUTOFF: u32 = 1; pub const RE_LI_OUTER_CUTOFF: u32 = 2; pub const RE_LI_DIRECTION: u32 = 4; pub const RE_LI_FOV: u32 = 8;
+pub const RE_WL_DIRECTIONAL: usize = 0; pub const RE_WL_POINT: usize = 1; pub const RE_WL_SPOT: usize = 2;

@@ -157,6 +157,31 @@ impl GpuVisibleSet {
         }
     }
 
+    /// ECS::write_component::<LightInformation> for a batch of entities (None removes the component)
+    pub fn set_light_information(&mut self, ids: &[u32], infos: Option<&[ReLightInformation]>) -> Result<(), GpuError> {
+        if let Some(i) = infos { assert_eq!(i.len(), ids.len()); }
+        let p = infos.map_or(std::ptr::null(), |i| i.as_ptr());
+        self.check(unsafe { re_set_light_information(self.ctx, ids.as_ptr(), ids.len() as u32, p) })
+    }
+
+    /// RenderSystem::upload_{directional,point,spot}_lights of one render system's draw (render_system.rs:563-576) from this world into its lighting
+    /// context: the previous sets live in `lighting`.  Returns the slot ids per type (directional, point, spot; None = that type's arrays were kept) and
+    /// anyLightSourceVisible.
+    pub fn set_lights_from_world(&mut self, lighting: *mut ReLighting, projection_view: &[f32; 16], position: [f32; 3], direction: [f32; 3], far_draw: f32,
+                                 max_directional_lights: u32, no_light_source_cutoff: f32, default_diffuse_factor: f32) -> Result<(bool, [Option<Vec<u32>>; 3]), GpuError> {
+        let cam = ReCamera { projection_view: *projection_view, position, direction, far_draw, n_lod: 0, lod_min: [0.0; 8], lod_max: [0.0; 8] };
+        let args = ReWorldLightArgs { max_directional_lights, no_light_source_cutoff, default_diffuse_factor };
+        let mut out = MaybeUninit::<ReWorldLights>::zeroed();
+        let rc = unsafe { re_lighting_set_lights_from_world(lighting, self.ctx, &cam, &args, out.as_mut_ptr()) };
+        if rc != RE_OK {
+            let p = unsafe { re_lighting_last_error(lighting) };
+            return Err(GpuError { code: rc, message: if p.is_null() { String::new() } else { unsafe { CStr::from_ptr(p) }.to_string_lossy().into_owned() } });
+        }
+        let out = unsafe { out.assume_init() };
+        let slots = |t: usize| if out.n_slots[t] == 0 { None } else { Some(unsafe { std::slice::from_raw_parts(out.slot_ids[t], out.n_slots[t] as usize) }.to_vec()) };
+        Ok((out.any_light_source_visible != 0, [slots(RE_WL_DIRECTIONAL), slots(RE_WL_POINT), slots(RE_WL_SPOT)]))
+    }
+
     // ---- several GPUs (one GpuVisibleSet per GPU, one process per GPU): the frame's exchange steps -------------------------------------------------
     /// rank 0 creates the id and hands it to the other ranks over the host's own channel
     pub fn comm_unique_id() -> Result<[u8; RE_COMM_ID_BYTES], GpuError> {

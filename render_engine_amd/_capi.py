@@ -56,7 +56,7 @@ CFG_PROBE_ALWAYS = 0x8
 CHANGE_MODIFY, CHANGE_DELETE, CHANGE_MAKE_STATIC, CHANGE_WAKE_UP, CHANGE_REMOVE_COMPONENT, CHANGE_ADD_ENTITY, CHANGE_ADD_SORTABLE, CHANGE_REMOVE_SORTABLE = 0, 1, 2, 3, 4, 5, 6, 7
 # bit positions of re_ecs_bitset == registration order of the reference (ECS::new + LogicFlow::new)
 ECS_BIT = dict(TYPE_IDENTIFIER=0, CAN_CAUSE_COLLISIONS=2, HAS_MOVED=3, POSITION=4, VELOCITY=5, ACCELERATION=6, HAS_ROTATED=7, ROTATION=8, VELOCITY_ROTATION=9,
-               ACCELERATION_ROTATION=10, SCALE=11, TRANSFORMATION=12, MODEL_ID=13, STATIC_AABB=15, ORIGINAL_AABB=16, ALWAYS_EXECUTE_LOGIC=20)
+               ACCELERATION_ROTATION=10, SCALE=11, TRANSFORMATION=12, MODEL_ID=13, STATIC_AABB=15, ORIGINAL_AABB=16, LIGHT_INFORMATION=19, ALWAYS_EXECUTE_LOGIC=20)
 
 
 class TypeIds(C.Structure):
@@ -103,13 +103,33 @@ class Lights(C.Structure):
                [("camera_pos", C.c_float * 3), ("no_light_source_cutoff", C.c_float), ("default_diffuse_factor", C.c_float), ("any_light_source_visible", C.c_uint32)]
 
 
+# LightInformation (re_light_information, 80 bytes) and the from-world light upload (re_lighting_set_lights_from_world)
+C_LIGHT_INFORMATION, ECS_BIT_LIGHT_INFORMATION = 11, 19
+LI_CUTOFF, LI_OUTER_CUTOFF, LI_DIRECTION, LI_FOV = 1, 2, 4, 8
+WL_DIRECTIONAL, WL_POINT, WL_SPOT = 0, 1, 2
+
+
+class LightInformation(C.Structure):
+    _fields_ = [("radius", C.c_float), ("diffuse", C.c_float * 3), ("specular", C.c_float * 3), ("ambient", C.c_float * 4), ("linear", C.c_float),
+                ("quadratic", C.c_float), ("cutoff", C.c_float), ("outer_cutoff", C.c_float), ("direction", C.c_float * 3), ("fov", C.c_float),
+                ("present", C.c_uint32)]
+
+
+class WorldLightArgs(C.Structure):
+    _fields_ = [("max_directional_lights", C.c_uint32), ("no_light_source_cutoff", C.c_float), ("default_diffuse_factor", C.c_float)]
+
+
+class WorldLights(C.Structure):
+    _fields_ = [("any_light_source_visible", C.c_uint32), ("n_nearby", C.c_uint32 * 3), ("n_slots", C.c_uint32 * 3), ("slot_ids", C.POINTER(C.c_uint32) * 3)]
+
+
 # every symbol include/re_hip.h declares
 EXPORTS = ["re_create", "re_destroy", "re_last_error", "re_abi_version", "re_upload_entities", "re_set_model_lod", "re_cull_pack", "re_tick",
-           "re_apply_changes", "re_apply_changes_ex", "re_add_entities", "re_set_shard_range", "re_list_migrants", "re_export_entities", "re_collide", "re_wait", "re_run_frames", "re_comm_unique_id", "re_comm_init", "re_comm_adopt", "re_comm_destroy", "re_allgather_visible", "re_gather_wait", "re_copy_visible", "re_set_output_buffers", "re_set_output_count", "re_read_component", "re_ecs_bitset", "re_ecs_query", "re_visible_lights", "re_section_keys", "re_get_out_of_bounds", "re_get_stats",
+           "re_apply_changes", "re_apply_changes_ex", "re_add_entities", "re_set_shard_range", "re_list_migrants", "re_export_entities", "re_collide", "re_wait", "re_run_frames", "re_comm_unique_id", "re_comm_init", "re_comm_adopt", "re_comm_destroy", "re_allgather_visible", "re_gather_wait", "re_copy_visible", "re_set_output_buffers", "re_set_output_count", "re_read_component", "re_set_light_information", "re_ecs_bitset", "re_ecs_query", "re_visible_lights", "re_section_keys", "re_get_out_of_bounds", "re_get_stats",
            "re_debug_get_sections", "re_debug_get_shared_sections", "re_debug_get_visible_sections", "re_debug_copy_to_host", "re_get_timings", "re_get_stream",
            "re_timing_begin", "re_timing_collect", "re_get_last_candidates", "re_debug_get_plan_stats",
            "re_lighting_create", "re_lighting_destroy", "re_lighting_last_error", "re_lighting_upload_gbuffer", "re_lighting_set_lights",
-           "re_lighting_run", "re_lighting_read", "re_lighting_read_pixels",
+           "re_lighting_run", "re_lighting_read", "re_lighting_read_pixels", "re_lighting_set_lights_from_world",
            "re_history_create", "re_history_destroy", "re_history_last_error", "re_history_set_state", "re_history_get_state", "re_history_record",
            "re_history_count", "re_history_get", "re_history_encode", "re_history_write", "re_history_load"]
 
@@ -170,6 +190,7 @@ def load():
     L.re_read_component.restype = C.c_int; L.re_read_component.argtypes = [vp, C.c_uint32, C.c_int, vp]
     L.re_ecs_bitset.restype = C.c_int; L.re_ecs_bitset.argtypes = [vp, C.c_uint32, _u32p]
     L.re_section_keys.restype = C.c_int; L.re_section_keys.argtypes = [C.POINTER(Config), C.POINTER(Entities), vp, vp]
+    L.re_set_light_information.restype = C.c_int; L.re_set_light_information.argtypes = [vp, vp, C.c_uint32, vp]
     L.re_visible_lights.restype = C.c_int; L.re_visible_lights.argtypes = [vp, C.POINTER(CameraC), C.c_uint32, vp, C.c_uint32, _u32p]
     L.re_ecs_query.restype = C.c_int; L.re_ecs_query.argtypes = [vp, C.POINTER(C.c_int), C.c_uint32, vp, C.c_uint32, _u32p]
     L.re_get_out_of_bounds.restype = C.c_int; L.re_get_out_of_bounds.argtypes = [vp, vp, C.c_uint32, _u32p]
@@ -193,6 +214,8 @@ def load():
     L.re_lighting_run.restype = C.c_int; L.re_lighting_run.argtypes = [vp, _fp]
     L.re_lighting_read.restype = C.c_int; L.re_lighting_read.argtypes = [vp, vp]
     L.re_lighting_read_pixels.restype = C.c_int; L.re_lighting_read_pixels.argtypes = [vp, vp, C.c_uint32, vp]
+    L.re_lighting_set_lights_from_world.restype = C.c_int
+    L.re_lighting_set_lights_from_world.argtypes = [vp, vp, C.POINTER(CameraC), C.POINTER(WorldLightArgs), C.POINTER(WorldLights)]
     L.re_history_create.restype = C.c_int; L.re_history_create.argtypes = [C.POINTER(TypeIds), C.c_uint32, C.POINTER(vp)]
     L.re_history_destroy.restype = None; L.re_history_destroy.argtypes = [vp]
     L.re_history_last_error.restype = C.c_char_p; L.re_history_last_error.argtypes = [vp]

@@ -22,6 +22,7 @@
 #include "re_guard.h"
 #include "re_kernels.h"
 #include "re_math.h"
+#include "re_world_lights.h"
 
 using namespace re;
 
@@ -237,7 +238,9 @@ struct re_ctx {
     } rb2;
     std::vector<uint32_t> stale_slots;                   // sections patched on the device since the host mirrors (h_cell_*, h_rows, h_row_*, extra_slots) were last brought up to date
     uint32_t n_device_rebuckets = 0, n_host_rebuckets = 0, n_phantom = 0, last_added_rejected = 0, slack_boost = 1;
-    std::vector<uint32_t> h_light_rows; DevBuf<uint32_t> d_light_rows, d_light_out; bool light_rows_dirty = true;   // rows that carry a FindLightType (members of their section's light set)
+    std::vector<uint32_t> h_light_rows; DevBuf<uint32_t> d_light_rows, d_light_out; bool light_rows_dirty = true;   // rows that carry a FindLightType (members of their section's light set); ascending EntityId on the device
+    // LightInformation (re_set_light_information) by row: the host copy is the truth (nothing on the device writes it); the device column d_li follows the light list
+    std::unordered_map<uint32_t, re_light_information> h_li; std::vector<re_light_information> h_li_col; DevBuf<re_light_information> d_li; bool li_dirty = true; bool li_complete[3] = {};
     std::vector<hipEvent_t> k1_events; uint32_t k1_used = 0, k1_every = 1, k1_seen = 0, k1_kind = 0; bool k1_timing = false;   // per-launch timing of one kernel (re_timing_begin): k_scan_cull, k_tick or k_pack_large
 
     int fail(int code, const char *fmt, ...) {
@@ -330,6 +333,7 @@ static void release_rb2(re_ctx *c) {
 static void free_world(re_ctx *c) {
     uint64_t *a = &c->dev_bytes;
     c->d_light_rows.release(nullptr); c->d_light_out.release(nullptr); c->light_rows_dirty = true;
+    c->h_li.clear(); c->h_li_col.clear(); c->d_li.release(nullptr); c->li_dirty = true;
     c->d_cell_cap.release(a); c->d_cell_links.release(a); c->h_linked_slots.clear(); c->d_base_keys.release(a); c->d_ovl_keys.release(nullptr); c->d_ovl_slots.release(nullptr); c->rb_base_dirty = c->rb_ovl_dirty = true; c->stale_slots.clear();
     c->d_hrb_list.release(nullptr); c->d_hrb_nk.release(nullptr); c->d_hrb_keys.release(nullptr); c->d_chg_ops.release(nullptr); c->d_chg_list.release(nullptr);
     if (c->h_chg) { (void)hipHostFree(c->h_chg); c->h_chg = nullptr; c->d_chg = nullptr; }
@@ -3587,6 +3591,11 @@ extern "C" int re_read_component(re_ctx *c, uint32_t entity_id, int component, v
         case RE_C_ACCELERATION: if (!dynidx(j)) return c->fail(RE_E_ARG, "entity %u has no Acceleration", entity_id); HIPCHK(c, hipMemcpy(dst, c->d_dyn_acc.p + (size_t)j * 3, 12, hipMemcpyDeviceToHost)); break;
         case RE_C_ROTATION_VEL: if (!dynidx(j)) return c->fail(RE_E_ARG, "entity %u has no VelocityRotation", entity_id); HIPCHK(c, hipMemcpy(dst, c->d_dyn_rotvel.p + (size_t)j * 4, 16, hipMemcpyDeviceToHost)); break;
         case RE_C_ROTATION_ACC: if (!dynidx(j)) return c->fail(RE_E_ARG, "entity %u has no AccelerationRotation", entity_id); HIPCHK(c, hipMemcpy(dst, c->d_dyn_rotacc.p + (size_t)j * 4, 16, hipMemcpyDeviceToHost)); break;
+        case RE_C_LIGHT_INFORMATION: {
+            auto e = c->h_li.find(r);
+            if (e == c->h_li.end()) return c->fail(RE_E_ARG, "re_read_component: entity %u does not carry LightInformation", entity_id);
+            memcpy(dst, &e->second, sizeof(re_light_information)); break;
+        }
         default: return c->fail(RE_E_ARG, "re_read_component: unknown component %d", component);
     }
     return RE_OK;
@@ -3617,6 +3626,7 @@ extern "C" int re_ecs_bitset(re_ctx *c, uint32_t entity_id, uint32_t *bits) try 
     uint32_t fl = 0;
     HIPCHK(c, hipMemcpy(&fl, c->d_flags.p + r, 4, hipMemcpyDeviceToHost));     // the device column is the truth (HasMoved / HasRotated are maintained by the tick)
     *bits = ecs_bits_of_flags(fl);
+    if (!(fl & F_DEAD) && c->h_li.count(r)) *bits |= 1u << RE_ECS_BIT_LIGHT_INFORMATION;
     return RE_OK;
 } RE_ABI_GUARD(c, "re_ecs_bitset")
 // The world sections an entity is registered in -- one key (its unique section) or the 2..8 keys its shared section links --, for a loader that spreads
@@ -3648,6 +3658,76 @@ extern "C" int re_section_keys(const re_config *cfg, const re_entities *E, uint6
     return RE_OK;
 } RE_ABI_GUARD_NOCTX(g_create_error, "re_section_keys")
 
+// the light list on the device, in ascending EntityId (a removed entity and the one that reused its id: ascending row) -- the order in which
+// re_lighting_set_lights_from_world compacts the nearby lights.  The LightInformation column follows it.
+static int sync_light_rows(re_ctx *c) {
+    if (!c->light_rows_dirty) return RE_OK;
+    std::sort(c->h_light_rows.begin(), c->h_light_rows.end(), [&](uint32_t a, uint32_t b) { return c->h_id[a] != c->h_id[b] ? c->h_id[a] < c->h_id[b] : a < b; });
+    const uint32_t nl = (uint32_t)c->h_light_rows.size();
+    HIPCHK(c, c->d_light_rows.alloc(nl, nullptr));
+    if (nl) HIPCHK(c, hipMemcpy(c->d_light_rows.p, c->h_light_rows.data(), (size_t)nl * 4, hipMemcpyHostToDevice));
+    c->light_rows_dirty = false; c->li_dirty = true;
+    return RE_OK;
+}
+
+extern "C" int re_set_light_information(re_ctx *c, const uint32_t *entity_ids, uint32_t n, const re_light_information *info) try {
+    if (!c) return RE_E_ARG;
+    if (n && !entity_ids) return c->fail(RE_E_ARG, "re_set_light_information: entity_ids is NULL");
+    if (!c->h_res) return c->fail(RE_E_STATE, "re_set_light_information: no world uploaded");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc_ = resolve(c); if (rc_ != RE_OK) return rc_; }                     // (removals of the last tick are in h_flags)
+    std::vector<uint32_t> rows(n);
+    for (uint32_t i = 0; i < n; i++) {                                          // the whole batch is checked before anything is written
+        if (!c->row_of(entity_ids[i], &rows[i])) return c->fail(RE_E_ARG, "re_set_light_information: unknown entity %u", entity_ids[i]);
+        if (c->h_flags[rows[i]] & F_DEAD) return c->fail(RE_E_ARG, "re_set_light_information: entity %u was removed", entity_ids[i]);
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        if (info) { re_light_information v = info[i]; v.present &= RE_LI_CUTOFF | RE_LI_OUTER_CUTOFF | RE_LI_DIRECTION | RE_LI_FOV; c->h_li[rows[i]] = v; }
+        else c->h_li.erase(rows[i]);
+    }
+    if (n) c->li_dirty = true;
+    return RE_OK;
+} RE_ABI_GUARD(c, "re_set_light_information")
+
+// what re_lighting_set_lights_from_world needs of the world (re_world_lights.h)
+int re::world_lights_view(re_ctx *c, int device, const re_camera *cam, const uint32_t need[3], WorldLightsView *v, std::string *err) {
+    auto fail = [&](int code, const char *msg) { *err = msg; return code; };
+    if (c->device != device) return fail(RE_E_ARG, "re_lighting_set_lights_from_world: the world context and the lighting context are on different devices");
+    if (!c->h_res) return fail(RE_E_STATE, "re_lighting_set_lights_from_world: no world uploaded");
+    if (c->shard_hi) return fail(RE_E_UNSUPPORTED, "re_lighting_set_lights_from_world: the context holds a shard of the world (re_set_shard_range): it sees only its own lights");
+    auto ctx_fail = [&](int rc) { *err = c->err; return rc; };
+    if (hipSetDevice(c->device) != hipSuccess) return fail(RE_E_HIP, "re_lighting_set_lights_from_world: hipSetDevice failed");
+    { int rc_ = resolve(c); if (rc_ != RE_OK) return ctx_fail(rc_); }            // the section table is settled (movers of the last tick are in)
+    { int rc_ = sync_light_rows(c); if (rc_ != RE_OK) return ctx_fail(rc_); }
+    const uint32_t nl = (uint32_t)c->h_light_rows.size();
+    if (c->li_dirty) {
+        c->h_li_col.assign(std::max(nl, 1u), re_light_information{});
+        static const uint32_t type_bit[3] = { F_LIGHT_DIRECTIONAL, F_LIGHT_POINT, F_LIGHT_SPOT };
+        for (int t = 0; t < 3; t++) c->li_complete[t] = true;
+        for (uint32_t i = 0; i < nl; i++) {
+            const uint32_t r = c->h_light_rows[i];
+            auto e = c->h_li.find(r);
+            if (e != c->h_li.end()) { c->h_li_col[i] = e->second; c->h_li_col[i].present |= LI_HAS; }
+            if (c->h_flags[r] & F_DEAD) continue;
+            for (int t = 0; t < 3; t++) if ((c->h_flags[r] & type_bit[t]) && (c->h_li_col[i].present & need[t]) != need[t]) c->li_complete[t] = false;
+        }
+        if (c->d_li.n < c->h_li_col.size() && c->d_li.alloc(c->h_li_col.size(), nullptr) != hipSuccess) return fail(RE_E_HIP, "re_lighting_set_lights_from_world: device allocation failed");
+        if (hipMemcpy(c->d_li.p, c->h_li_col.data(), c->h_li_col.size() * sizeof(re_light_information), hipMemcpyHostToDevice) != hipSuccess) return fail(RE_E_HIP, "re_lighting_set_lights_from_world: copy of the LightInformation column failed");
+        c->li_dirty = false;
+    }
+    v->stream = c->stream; v->nl = nl;
+    v->light_rows = c->d_light_rows.p; v->flags = c->d_flags.p; v->row_id = c->d_id.p; v->row_cell = c->d_row_cell.p;
+    v->cell_key = c->d_cell_key.p; v->cell_flags = c->d_cell_flags.p; v->sh_cells = c->d_sh_cells.p; v->pos = c->d_pos.p; v->info = c->d_li.p;
+    const float r = cam->far_draw, wsl = (float)c->cfg.atomic_length;
+    v->Q = LightQuery{};
+    v->Q.culler = Aabb{ cam->position[0] - r, cam->position[0] + r, cam->position[1] - r, cam->position[1] + r, cam->position[2] - r, cam->position[2] + r };
+    fill_level_boxes(v->Q.box, c->maxlevel, wsl, rmax(cam->position[0] - r, 0.0f), cam->position[0] + r, rmax(cam->position[1] - r, 0.0f), cam->position[1] + r,
+                     rmax(cam->position[2] - r, 0.0f), cam->position[2] + r);   // the culler of re_visible_lights
+    v->Q.max_level = c->maxlevel; v->Q.type_flag = F_LIGHT_ANY;
+    for (int t = 0; t < 3; t++) v->complete[t] = c->li_complete[t];
+    return RE_OK;
+}
+
 // The lights of one type RenderFlow::render finds near the camera (flows/render_flow.rs:249-254 -> flows/shadow_flow.rs:455-513): k_visible_lights over the
 // entities uploaded with RE_F_LIGHT_*.  Stands alone (own visibility test with the AABB culler of radius far_draw); ids in ascending order.
 extern "C" int re_visible_lights(re_ctx *c, const re_camera *cam, uint32_t light_type, uint32_t *ids, uint32_t capacity, uint32_t *n_out) try {
@@ -3660,7 +3740,7 @@ extern "C" int re_visible_lights(re_ctx *c, const re_camera *cam, uint32_t light
     *n_out = 0;
     const uint32_t nl = (uint32_t)c->h_light_rows.size();
     if (!nl) return RE_OK;
-    if (c->light_rows_dirty) { HIPCHK(c, c->d_light_rows.alloc(nl, nullptr)); HIPCHK(c, hipMemcpy(c->d_light_rows.p, c->h_light_rows.data(), (size_t)nl * 4, hipMemcpyHostToDevice)); c->light_rows_dirty = false; }
+    { int rc_ = sync_light_rows(c); if (rc_ != RE_OK) return rc_; }
     if (c->d_light_out.n < (size_t)nl + 1) HIPCHK(c, c->d_light_out.alloc((size_t)nl + 1, nullptr));
     LightQuery Q{}; const float r = cam->far_draw, wsl = (float)c->cfg.atomic_length;
     Q.culler = Aabb{ cam->position[0] - r, cam->position[0] + r, cam->position[1] - r, cam->position[1] + r, cam->position[2] - r, cam->position[2] + r };

@@ -362,6 +362,20 @@ __global__ void k_rb_gather_keys(uint32_t n, const uint32_t *perm, const uint64_
 __global__ void k_rb_gather_cells(uint32_t n, const uint32_t *slots, RbCells C, uint64_t *out_key, uint32_t *out_hdr);
 __global__ void k_rb_gather_rows(uint32_t n, const uint32_t *slots, const uint32_t *offs, RbCells C, uint32_t *out_rows);
 struct LightQuery { LevelBox box[MAX_LEVELS]; Aabb culler; uint32_t max_level, type_flag; };
+__device__ __forceinline__ bool in_box(uint32_t x, uint32_t y, uint32_t z, const LevelBox &b) {
+    return ((x - b.bx) & 0xFFFFu) < b.nx && ((y - b.by) & 0xFFFFu) < b.ny && ((z - b.bz) & 0xFFFFu) < b.nz;
+}
+__device__ __forceinline__ bool light_section_visible(uint64_t key, const LightQuery &Q) {
+    const uint32_t lv = key_level(key);
+    if (lv >= Q.max_level) return false;
+    const LevelBox b = Q.box[lv];
+    const uint32_t x = key_x(key), y = key_y(key), z = key_z(key);
+    if (!in_box(x, y, z, b)) return false;
+    const float ll = b.level_length;
+    const float fx = (float)(b.bx + ((x - b.bx) & 0xFFFFu)) * ll, fy = (float)(b.by + ((y - b.by) & 0xFFFFu)) * ll, fz = (float)(b.bz + ((z - b.bz) & 0xFFFFu)) * ll;   // visible_world_flow.rs:73-82
+    const Aabb &c = Q.culler;
+    return c.xmin <= fx + ll && c.xmax >= fx && c.ymin <= fy + ll && c.ymax >= fy && c.zmin <= fz + ll && c.zmax >= fz;      // StaticAABB::intersect (aabb.rs:68-73)
+}
 __global__ void k_visible_lights(uint32_t n, const uint32_t *light_rows, const uint32_t *flags, const uint32_t *row_id, const uint32_t *row_cell, const uint64_t *cell_key,
                                  const uint8_t *cell_flags, const int32_t *sh_cells, LightQuery Q, uint32_t *out_ids, uint32_t cap, uint32_t *count);
 __global__ void k_scatter32(uint32_t m, const Pair32 *pairs, uint32_t *dst);

@@ -257,9 +257,6 @@ __device__ __forceinline__ bool pk_in_box(uint32_t hi, uint32_t lo, const PBox &
     uint32_t dh = pk_sub_u16(hi, b.sub_hi), dl = pk_sub_u16(lo, b.sub_lo);
     return (pk_min_u16(dh, b.min_hi) == dh) && (pk_min_u16(dl, b.min_lo) == dl);
 }
-__device__ __forceinline__ bool in_box(uint32_t x, uint32_t y, uint32_t z, const LevelBox &b) {
-    return ((x - b.bx) & 0xFFFFu) < b.nx && ((y - b.by) & 0xFFFFu) < b.ny && ((z - b.bz) & 0xFFFFu) < b.nz;
-}
 
 // Visibility of one world section of level-box pair (a = logic, b = render): 0 = not visible, 1 = in one of the two
 // query results, 2 = in both (the section then appears twice in visible_sections_vec).  *candidate: inside a candidate box.
@@ -1846,17 +1843,7 @@ __global__ __launch_bounds__(256) void k_rb_gather_rows(uint32_t n, const uint32
 // whole-world visibility query with an AABB culler of radius far_draw; then find_nearby_lights :455-487: the light sets of those unique sections and
 // of the shared sections linked to them, world/bounding_box_tree_v2.rs:157-228).  One thread per light entity: is the section that holds it (or, for
 // an entity of a shared section, any of the linked sections) a candidate of its level's box whose grid AABB intersects the culler?
-__device__ __forceinline__ bool light_section_visible(uint64_t key, const LightQuery &Q) {
-    const uint32_t lv = key_level(key);
-    if (lv >= Q.max_level) return false;
-    const LevelBox b = Q.box[lv];
-    const uint32_t x = key_x(key), y = key_y(key), z = key_z(key);
-    if (!in_box(x, y, z, b)) return false;
-    const float ll = b.level_length;
-    const float fx = (float)(b.bx + ((x - b.bx) & 0xFFFFu)) * ll, fy = (float)(b.by + ((y - b.by) & 0xFFFFu)) * ll, fz = (float)(b.bz + ((z - b.bz) & 0xFFFFu)) * ll;   // visible_world_flow.rs:73-82
-    const Aabb &c = Q.culler;
-    return c.xmin <= fx + ll && c.xmax >= fx && c.ymin <= fy + ll && c.ymax >= fy && c.zmin <= fz + ll && c.zmax >= fz;      // StaticAABB::intersect (aabb.rs:68-73)
-}
+// (light_section_visible: re_kernels.h)
 __global__ __launch_bounds__(256) void k_visible_lights(uint32_t n, const uint32_t *__restrict__ light_rows, const uint32_t *__restrict__ flags, const uint32_t *__restrict__ row_id,
                                                         const uint32_t *__restrict__ row_cell, const uint64_t *__restrict__ cell_key, const uint8_t *__restrict__ cell_flags,
                                                         const int32_t *__restrict__ sh_cells, LightQuery Q, uint32_t *__restrict__ out_ids, uint32_t cap, uint32_t *count) {

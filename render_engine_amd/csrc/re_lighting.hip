@@ -24,6 +24,7 @@
 #include <vector>
 #include "re_hip.h"
 #include "re_guard.h"
+#include "re_world_lights.h"
 
 namespace {
 
@@ -119,11 +120,20 @@ __device__ __forceinline__ void shade_pair(const PixelPair &X, bool live0, bool 
     ax += cx; ay += cy; az += cz;
 }
 
-__global__ __launch_bounds__(LT_THREADS) void k_deferred_lighting(LightParams P, const float4 *__restrict__ gpos, const float4 *__restrict__ gnormal, const uchar4 *__restrict__ galbedo,
+// DEV = false: the parameters come with the launch (re_lighting_set_lights); DEV = true: the light counts, the slab parameters, the camera and the factors are
+// read from the device block the from-world upload wrote (re_lighting_set_lights_from_world), so that nothing of them has to come back to the host.
+template <bool DEV>
+__global__ __launch_bounds__(LT_THREADS) void k_deferred_lighting(LightParams Parg, const float4 *__restrict__ gpos, const float4 *__restrict__ gnormal, const uchar4 *__restrict__ galbedo,
                                                                    const float4 *__restrict__ spot,     // 4 float4 per light: A, B, C, D (slab order)
                                                                    const uint32_t *__restrict__ slab_start,   // LIGHT_BUCKETS + 1: first record of each slab
                                                                    const float4 *__restrict__ point,    // 5 float4 per light: A(pos), B, C, D, E(dir.xyz normalised, -) + F(cutoff, outer, -, -) packed as 6
-                                                                   float4 *__restrict__ out) {
+                                                                   float4 *__restrict__ out, const LightParams *__restrict__ dparams) {
+    LightParams P = Parg;
+    if constexpr (DEV) {
+        const LightParams D = *dparams;
+        P.n_spot = D.n_spot; P.n_point = D.n_point; P.cam[0] = D.cam[0]; P.cam[1] = D.cam[1]; P.cam[2] = D.cam[2]; P.cutoff = D.cutoff; P.default_diffuse = D.default_diffuse;
+        P.any_visible = D.any_visible; P.axis = D.axis; P.kmin = D.kmin; P.inv_w = D.inv_w; P.rmax = D.rmax;
+    }
     __shared__ float s_red[4][6];
     __shared__ float4 s_rec[LIST_CAP * 4];                                    // the listed lights' records (A, B, C, D)
     __shared__ uint32_t s_wcnt[4];
@@ -272,6 +282,252 @@ __global__ void k_gather_pixels(const float4 *img, const uint32_t *idx, uint32_t
     if (i < n) out[i] = img[idx[i]];
 }
 
+
+// ---- from-world upload (re_lighting_set_lights_from_world): upload_directional_lights / upload_point_lights / upload_spot_lights of RenderSystem::draw
+// (render_system/render_system.rs:681-845) on the device, two single-workgroup launches on the world context's stream:
+//   k_world_select: the nearby test of every light of the list (ascending EntityId), previous ∩ nearby, the slots (existing ++ nearby, take N) and the
+//                   next previous set, into scratch -- nothing the renderer reads is written, so a failed check leaves everything as it was;
+//   k_world_commit: the previous sets, the records in K5's layouts (live positions), the slab table of the radius lights, the device parameter block.
+// Type index t: 0 directional, 1 point ("cone"), 2 spot ("radius") -- RE_WL_*.
+constexpr int WL_THREADS = 1024, WL_WAVES = WL_THREADS / 64, SEL_THREADS = 512, SEL_WAVES = SEL_THREADS / 64;   // (the selection at 1024 threads spilled: 128 VGPRs)
+constexpr uint32_t WL_LDS_BUCKETS = 8192;   // spot slots whose slab index the stable placement reads from LDS (the rest from the scratch array)
+struct WorldSel { uint32_t n_prev[3], n_nearby[3], n_slots[3], n_stage[3], bad_id, pad; };
+struct WorldSelArgs {
+    uint32_t nl; const uint32_t *rows, *flags, *row_id, *row_cell; const uint64_t *cell_key; const uint8_t *cell_flags; const int32_t *sh_cells;
+    const re_light_information *info; uint32_t max[3], need[3];
+    const uint32_t *prev[3]; uint32_t *stage[3], *slot_li[3], *slot_id[3], *lmask; WorldSel *sel;
+};
+struct WorldCommitArgs {
+    WorldSel *sel; const uint32_t *slot_li[3], *stage[3]; uint32_t *prev[3];
+    const uint32_t *rows; const float *pos; const re_light_information *info;
+    uint32_t max_spot; float cam[3], cutoff, default_diffuse;
+    float4 *spot; uint32_t *slab; float4 *point; LightParams *params; uint32_t *place;
+};
+__device__ __forceinline__ bool in_sorted(const uint32_t *a, uint32_t n, uint32_t v) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (a[m] < v) lo = m + 1u; else hi = m; }
+    return lo < n && a[lo] == v;
+}
+__device__ __forceinline__ uint32_t lanes_below(uint64_t m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
+
+__global__ __launch_bounds__(SEL_THREADS) void k_world_select(WorldSelArgs A, re::LightQuery Qarg) {
+    __shared__ uint32_t s_tot[6], s_wc[SEL_WAVES][6];
+    __shared__ re::LightQuery Q;                                              // (the level boxes are indexed by a section's level: from LDS, not a private copy of the argument)
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
+    if (tid == 0) Q = Qarg;
+    const uint32_t type_bit[3] = { re::F_LIGHT_DIRECTIONAL, re::F_LIGHT_POINT, re::F_LIGHT_SPOT };
+    uint32_t nprev[3];
+    #pragma unroll
+    for (int t = 0; t < 3; t++) nprev[t] = A.sel->n_prev[t];
+    __syncthreads();                                                          // (every thread has read the counts before thread 0 resets the check)
+    if (tid < 6) s_tot[tid] = 0u;
+    if (tid == 0) A.sel->bad_id = 0xFFFFFFFFu;
+    __syncthreads();
+    // pass 1: per light, bit t = nearby light of type t (find_nearby_lights: re_visible_lights' test), bit 3 + t = also in previous_t
+    for (uint32_t base = 0; base < A.nl; base += SEL_THREADS) {
+        const uint32_t i = base + tid; uint32_t m = 0;
+        if (i < A.nl) {
+            const uint32_t r = A.rows[i], fl = A.flags[r], rc = A.row_cell[r];
+            if (!(fl & re::F_DEAD) && (fl & re::F_LIGHT_ANY) && rc != re::ROW_CELL_NONE) {
+                bool vis = false;
+                if (!(rc & re::ROW_CELL_SHARED)) vis = !(A.cell_flags[rc] & re::CF_PAD) && re::light_section_visible(A.cell_key[rc], Q);
+                else {
+                    const uint32_t sh = rc & ~re::ROW_CELL_SHARED;
+                    #pragma unroll
+                    for (int k = 0; k < 8 && !vis; k++) { const int32_t c = A.sh_cells[sh * 8 + k]; if (c >= 0 && !(A.cell_flags[c] & re::CF_PAD)) vis = re::light_section_visible(A.cell_key[c], Q); }
+                }
+                if (vis) {
+                    const uint32_t id = A.row_id[r];
+                    #pragma unroll
+                    for (int t = 0; t < 3; t++) if (fl & type_bit[t]) { m |= 1u << t; if (in_sorted(A.prev[t], nprev[t], id)) m |= 8u << t; }
+                }
+            }
+            A.lmask[i] = m;
+        }
+        #pragma unroll
+        for (int q = 0; q < 6; q++) { const uint64_t b = __ballot((m >> q) & 1u); if (lane == 0 && b) atomicAdd(&s_tot[q], (uint32_t)__popcll(b)); }
+    }
+    __syncthreads();
+    // N = min(|nearby|, max); slots = existing[0 .. min(|existing|, N)) ++ nearby[0 .. K), K = N - min(|existing|, N)
+    uint32_t take[3], ne[3], K[3];
+    #pragma unroll
+    for (int t = 0; t < 3; t++) { take[t] = min(s_tot[t], A.max[t]); ne[t] = min(s_tot[3 + t], take[t]); K[t] = take[t] - ne[t]; }
+    // pass 2: order-preserving compaction (ballot ranks + per-wave counts; carries across rounds)
+    uint32_t cj[3] = { 0, 0, 0 }, ce[3] = { 0, 0, 0 }, cp[3] = { 0, 0, 0 };
+    for (uint32_t base = 0; base < A.nl; base += SEL_THREADS) {
+        const uint32_t i = base + tid;
+        const uint32_t m = i < A.nl ? A.lmask[i] : 0u;                        // (written by this thread in pass 1)
+        uint64_t b[6];
+        #pragma unroll
+        for (int q = 0; q < 6; q++) b[q] = __ballot((m >> q) & 1u);
+        if (lane == 0)
+#pragma unroll
+            for (int q = 0; q < 6; q++) s_wc[wid][q] = (uint32_t)__popcll(b[q]);
+        __syncthreads();
+        uint32_t pre[6], tot[6];
+        #pragma unroll
+        for (int q = 0; q < 6; q++) { pre[q] = tot[q] = 0; for (uint32_t w = 0; w < SEL_WAVES; w++) { const uint32_t v = s_wc[w][q]; tot[q] += v; if (w < wid) pre[q] += v; } }
+        __syncthreads();                                                      // (s_wc is reused below)
+        uint32_t id = 0, present = 0, keep = 0;
+        if (m) { id = A.row_id[A.rows[i]]; present = A.info[i].present; }
+        #pragma unroll
+        for (int t = 0; t < 3; t++) {
+            const uint32_t j = cj[t] + pre[t] + lanes_below(b[t]), k = ce[t] + pre[3 + t] + lanes_below(b[3 + t]);
+            const bool sel_e = ((m >> (3 + t)) & 1u) && k < take[t], sel_n = ((m >> t) & 1u) && j < K[t];
+            if (sel_e) { A.slot_li[t][k] = i; A.slot_id[t][k] = id; }
+            if (sel_n) { A.slot_li[t][ne[t] + j] = i; A.slot_id[t][ne[t] + j] = id; }
+            if ((sel_e || sel_n) && (present & A.need[t]) != A.need[t]) atomicMin(&A.sel->bad_id, id);   // get_ref::<LightInformation>(id).unwrap() / an unwrapped field
+            if (sel_e || sel_n) keep |= 1u << t;
+            cj[t] += tot[t]; ce[t] += tot[3 + t];
+        }
+        uint64_t bk[3];
+        #pragma unroll
+        for (int t = 0; t < 3; t++) bk[t] = __ballot((keep >> t) & 1u);
+        if (lane == 0)
+#pragma unroll
+            for (int t = 0; t < 3; t++) s_wc[wid][t] = (uint32_t)__popcll(bk[t]);
+        __syncthreads();
+        #pragma unroll
+        for (int t = 0; t < 3; t++) {
+            uint32_t p = 0, tt = 0;
+            for (uint32_t w = 0; w < SEL_WAVES; w++) { const uint32_t v = s_wc[w][t]; tt += v; if (w < wid) p += v; }
+            if ((keep >> t) & 1u) A.stage[t][cp[t] + p + lanes_below(bk[t])] = id;   // the next previous set, ascending
+            cp[t] += tt;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) for (int t = 0; t < 3; t++) { A.sel->n_nearby[t] = s_tot[t]; A.sel->n_slots[t] = s_tot[t] ? take[t] : 0u; A.sel->n_stage[t] = cp[t]; }
+}
+
+// a radius light's 64-byte record (A = position, radius; B = diffuse, linear; C = specular, quadratic; D = ambient), as re_lighting_set_lights writes it;
+// the slots past the selection are all zeros (upload_spot_lights leaves them at their defaults, numberSpotLights = max_spot_lights)
+__device__ __forceinline__ void spot_record(const WorldCommitArgs &A, uint32_t s, uint32_t n, float4 &a, float4 &b, float4 &c, float4 &d) {
+    a = b = c = d = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (s >= n) return;
+    const uint32_t li = A.slot_li[2][s], r = A.rows[li];
+    const re_light_information &I = A.info[li];
+    a = make_float4(A.pos[(size_t)r * 3], A.pos[(size_t)r * 3 + 1], A.pos[(size_t)r * 3 + 2], I.radius);
+    b = make_float4(I.diffuse[0], I.diffuse[1], I.diffuse[2], I.linear);
+    c = make_float4(I.specular[0], I.specular[1], I.specular[2], I.quadratic);
+    d = make_float4(I.ambient[0], I.ambient[1], I.ambient[2], I.ambient[3]);
+}
+
+__global__ __launch_bounds__(WL_THREADS) void k_world_commit(WorldCommitArgs A) {
+    __shared__ uint32_t s_hist[LIGHT_BUCKETS + 1u], s_fill[LIGHT_BUCKETS], s_wt[WL_WAVES], s_axis;
+    __shared__ uint16_t s_b[WL_LDS_BUCKETS];
+    __shared__ float s_red[WL_WAVES][7], s_par[3];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
+    uint32_t nn[3], ns[3], nst[3];
+    #pragma unroll
+    for (int t = 0; t < 3; t++) { nn[t] = A.sel->n_nearby[t]; ns[t] = A.sel->n_slots[t]; nst[t] = A.sel->n_stage[t]; }
+    // previous_t := the lights taken, for the types that found any (a type without nearby lights returns before it clears its set)
+    #pragma unroll
+    for (int t = 0; t < 3; t++) if (nn[t]) {
+        for (uint32_t k = tid; k < nst[t]; k += WL_THREADS) A.prev[t][k] = A.stage[t][k];
+        if (tid == 0) A.sel->n_prev[t] = nst[t];
+    }
+    if (tid == 0) {
+        LightParams *P = A.params;
+        P->cam[0] = A.cam[0]; P->cam[1] = A.cam[1]; P->cam[2] = A.cam[2]; P->cutoff = A.cutoff; P->default_diffuse = A.default_diffuse;
+        P->any_visible = (nn[0] || nn[1] || nn[2]) ? 1u : 0u;               // anyLightSourceVisible: the OR of the three uploads, directional included
+    }
+    // cone lights (upload_point_lights :752-780): numberPointLights = N
+    if (nn[1]) {
+        for (uint32_t s = tid; s < ns[1]; s += WL_THREADS) {
+            const uint32_t li = A.slot_li[1][s], r = A.rows[li];
+            const re_light_information &I = A.info[li];
+            float4 *o = A.point + (size_t)s * 6;
+            o[0] = make_float4(A.pos[(size_t)r * 3], A.pos[(size_t)r * 3 + 1], A.pos[(size_t)r * 3 + 2], 0.f);
+            o[1] = make_float4(I.diffuse[0], I.diffuse[1], I.diffuse[2], I.linear);
+            o[2] = make_float4(I.specular[0], I.specular[1], I.specular[2], I.quadratic);
+            o[3] = make_float4(I.ambient[0], I.ambient[1], I.ambient[2], I.ambient[3]);
+            const float *d = I.direction; const float n = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);     // normalize(pointLightDirection[i]), as re_lighting_set_lights
+            o[4] = make_float4(d[0] / n, d[1] / n, d[2] / n, 0.f);
+            o[5] = make_float4(I.cutoff, I.outer_cutoff, 0.f, 0.f);
+        }
+        if (tid == 0) A.params->n_point = ns[1];
+    }
+    if (!nn[2]) return;                                                       // (uniform)
+    // radius lights (upload_spot_lights :814-839): all max_spot_lights slots, then the slab table exactly as re_lighting_set_lights builds it
+    const uint32_t M = A.max_spot, N = ns[2];
+    float mn[3] = { 3.4e38f, 3.4e38f, 3.4e38f }, mx[3] = { -3.4e38f, -3.4e38f, -3.4e38f }, rm = 0.0f;
+    for (uint32_t s = tid; s < M; s += WL_THREADS) {
+        float4 a, b, c, d; spot_record(A, s, N, a, b, c, d);
+        const float v[3] = { a.x, a.y, a.z };
+        #pragma unroll
+        for (int k = 0; k < 3; k++) { if (v[k] < mn[k]) mn[k] = v[k]; if (v[k] > mx[k]) mx[k] = v[k]; }   // (comparisons: NaN takes no part, as on the host)
+        if (a.w > rm) rm = a.w;
+    }
+    for (int d = 32; d >= 1; d >>= 1)
+        #pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const float o1 = __shfl_xor(mn[k], d, 64), o2 = __shfl_xor(mx[k], d, 64); if (o1 < mn[k]) mn[k] = o1; if (o2 > mx[k]) mx[k] = o2;
+            if (k == 0) { const float o3 = __shfl_xor(rm, d, 64); if (o3 > rm) rm = o3; }
+        }
+    if (lane == 0) { for (int k = 0; k < 3; k++) { s_red[wid][k] = mn[k]; s_red[wid][3 + k] = mx[k]; } s_red[wid][6] = rm; }
+    for (uint32_t b = tid; b < LIGHT_BUCKETS + 1u; b += WL_THREADS) s_hist[b] = 0u;
+    __syncthreads();
+    if (tid == 0) {
+        for (uint32_t w = 1; w < WL_WAVES; w++) {
+            #pragma unroll
+            for (int k = 0; k < 3; k++) { if (s_red[w][k] < mn[k]) mn[k] = s_red[w][k]; if (s_red[w][3 + k] > mx[k]) mx[k] = s_red[w][3 + k]; }
+            if (s_red[w][6] > rm) rm = s_red[w][6];
+        }
+        uint32_t axis = 0; float kmin = 0.0f, inv_w = 0.0f, best = -1.0f;
+        #pragma unroll
+        for (int k = 0; k < 3; k++) { const float e = mx[k] - mn[k]; if (e > best && e < 3.0e38f) { best = e; axis = (uint32_t)k; } }
+        if (best > 0.0f) { kmin = mn[axis]; inv_w = (float)LIGHT_BUCKETS / best; if (!(inv_w < 3.0e38f)) inv_w = 0.0f; }
+        s_axis = axis; s_par[0] = kmin; s_par[1] = inv_w; s_par[2] = rm;
+        A.params->n_spot = M; A.params->axis = axis; A.params->kmin = kmin; A.params->inv_w = inv_w; A.params->rmax = rm;
+    }
+    __syncthreads();
+    const uint32_t axis = s_axis; const float kmin = s_par[0], inv_w = s_par[1];
+    for (uint32_t s = tid; s < M; s += WL_THREADS) {
+        float4 a, b, c, d; spot_record(A, s, N, a, b, c, d);
+        const uint32_t bk = light_bucket(axis == 0 ? a.x : (axis == 1 ? a.y : a.z), kmin, inv_w);
+        atomicAdd(&s_hist[bk + 1u], 1u);
+        if (s < WL_LDS_BUCKETS) s_b[s] = (uint16_t)bk; else A.place[s] = bk;
+    }
+    __syncthreads();
+    // slab starts: inclusive prefix over s_hist[1 .. LIGHT_BUCKETS] (four entries per thread, then across the lanes and the waves)
+    static_assert(LIGHT_BUCKETS == 4u * WL_THREADS, "four slabs per thread");
+    uint32_t v[4], run = 0;
+    #pragma unroll
+    for (int k = 0; k < 4; k++) { run += s_hist[1u + 4u * tid + k]; v[k] = run; }
+    uint32_t incl = run;
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(incl, d, 64); if (lane >= (uint32_t)d) incl += o; }
+    if (lane == 63) s_wt[wid] = incl;
+    __syncthreads();
+    uint32_t off = incl - run;
+    for (uint32_t w = 0; w < wid; w++) off += s_wt[w];
+    #pragma unroll
+    for (int k = 0; k < 4; k++) s_hist[1u + 4u * tid + k] = off + v[k];
+    __syncthreads();
+    for (uint32_t b = tid; b < LIGHT_BUCKETS + 1u; b += WL_THREADS) { A.slab[b] = s_hist[b]; if (b < LIGHT_BUCKETS) s_fill[b] = s_hist[b]; }
+    __syncthreads();
+    // stable placement (ascending slot index inside a slab): one wave walks the slots 64 at a time; the lanes of one slab find each other with 12 ballots
+    if (wid == 0) {
+        for (uint32_t base = 0; base < M; base += 64u) {
+            const uint32_t s = base + lane; const bool valid = s < M;
+            const uint32_t bk = valid ? (s < WL_LDS_BUCKETS ? (uint32_t)s_b[s] : A.place[s]) : 0u;
+            uint64_t peers = __ballot(valid);
+            #pragma unroll
+            for (int bit = 0; bit < 12; bit++) { const bool on = (bk >> bit) & 1u; const uint64_t bb = __ballot(on); peers &= on ? bb : ~bb; }
+            static_assert(LIGHT_BUCKETS <= 4096u, "12 bits of slab index");
+            const uint32_t f = valid ? s_fill[bk] : 0u;
+            if (valid) {
+                A.place[s] = f + lanes_below(peers);
+                if ((peers >> lane) == 1ull) s_fill[bk] = f + (uint32_t)__popcll(peers);   // the slab's last lane of this step advances its fill
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t s = tid; s < M; s += WL_THREADS) {
+        float4 a, b, c, d; spot_record(A, s, N, a, b, c, d);
+        float4 *o = A.spot + (size_t)A.place[s] * 4;
+        o[0] = a; o[1] = b; o[2] = c; o[3] = d;
+    }
+}
 }  // namespace
 
 struct re_lighting {
@@ -280,6 +536,14 @@ struct re_lighting {
     std::string err;
     float4 *d_pos = nullptr, *d_nrm = nullptr, *d_out = nullptr, *d_spot = nullptr, *d_point = nullptr; uchar4 *d_alb = nullptr; uint32_t *d_slab = nullptr;
     LightParams P{};
+    // from-world uploads: K5 reads its light parameters from d_params after one (dev_params), from P after re_lighting_set_lights.  The previous sets of the three
+    // types (ascending ids) and the selection scratch; cap[t] = slots of type t (max_directional_lights grows with the largest one asked for)
+    LightParams *d_params = nullptr; bool dev_params = false;
+    WorldSel *d_sel = nullptr;
+    uint32_t *d_prev[3] = {}, *d_stage[3] = {}, *d_slot_li[3] = {}, *d_slot_id[3] = {}, cap[3] = {};
+    uint32_t *d_lmask = nullptr, lmask_cap = 0, *d_place = nullptr;
+    hipEvent_t ev_world = nullptr;
+    std::vector<uint32_t> h_slot_ids[3];
     int fail(int code, const char *fmt, ...) { char buf[512]; va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap); err = buf; return code; }
 };
 static thread_local std::string g_lt_error;
@@ -307,6 +571,9 @@ extern "C" void re_lighting_destroy(re_lighting *l) try {
     (void)hipSetDevice(l->cfg.device);
     if (l->stream) (void)hipStreamSynchronize(l->stream);
     (void)hipFree(l->d_pos); (void)hipFree(l->d_nrm); (void)hipFree(l->d_out); (void)hipFree(l->d_alb); (void)hipFree(l->d_spot); (void)hipFree(l->d_point); (void)hipFree(l->d_slab);
+    (void)hipFree(l->d_params); (void)hipFree(l->d_sel); (void)hipFree(l->d_lmask); (void)hipFree(l->d_place);
+    for (int t = 0; t < 3; t++) { (void)hipFree(l->d_prev[t]); (void)hipFree(l->d_stage[t]); (void)hipFree(l->d_slot_li[t]); (void)hipFree(l->d_slot_id[t]); }
+    if (l->ev_world) (void)hipEventDestroy(l->ev_world);
     if (l->stream) (void)hipStreamDestroy(l->stream);
     delete l;
 } catch (...) {}
@@ -367,6 +634,7 @@ extern "C" int re_lighting_set_lights(re_lighting *l, const re_lights *L) try {
     l->P.n_spot = L->n_spot; l->P.n_point = L->n_point; l->P.axis = axis; l->P.kmin = kmin; l->P.inv_w = inv_w; l->P.rmax = rmax;
     for (int k = 0; k < 3; k++) l->P.cam[k] = L->camera_pos[k];
     l->P.cutoff = L->no_light_source_cutoff; l->P.default_diffuse = L->default_diffuse_factor; l->P.any_visible = L->any_light_source_visible;
+    l->dev_params = false;
     return RE_OK;
 } RE_ABI_GUARD(l, "re_lighting_set_lights")
 extern "C" int re_lighting_run(re_lighting *l, float *kernel_us) try {
@@ -375,7 +643,10 @@ extern "C" int re_lighting_run(re_lighting *l, float *kernel_us) try {
     hipEvent_t a = nullptr, b = nullptr;
     if (kernel_us) { LCHK(l, hipEventCreate(&a)); LCHK(l, hipEventCreate(&b)); }
     dim3 grid((l->cfg.width + TILE - 1) / TILE, (l->cfg.height + TILE_H - 1) / TILE_H);
-    hipExtLaunchKernelGGL(k_deferred_lighting, grid, dim3(LT_THREADS), 0, l->stream, a, b, 0, l->P, l->d_pos, l->d_nrm, l->d_alb, l->d_spot, l->d_slab, l->d_point, l->d_out);
+    if (l->dev_params) hipExtLaunchKernelGGL(k_deferred_lighting<true>, grid, dim3(LT_THREADS), 0, l->stream, a, b, 0, l->P, l->d_pos, l->d_nrm, l->d_alb, l->d_spot, l->d_slab, l->d_point, l->d_out,
+                                             (const LightParams *)l->d_params);
+    else hipExtLaunchKernelGGL(k_deferred_lighting<false>, grid, dim3(LT_THREADS), 0, l->stream, a, b, 0, l->P, l->d_pos, l->d_nrm, l->d_alb, l->d_spot, l->d_slab, l->d_point, l->d_out,
+                               (const LightParams *)nullptr);
     LCHK(l, hipGetLastError());
     LCHK(l, hipStreamSynchronize(l->stream));
     if (kernel_us) { float ms = 0; LCHK(l, hipEventElapsedTime(&ms, a, b)); *kernel_us = ms * 1000.f; (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
@@ -399,3 +670,78 @@ extern "C" int re_lighting_read_pixels(re_lighting *l, const uint32_t *idx, uint
     (void)hipFree(d_idx); (void)hipFree(d_o);
     return RE_OK;
 } RE_ABI_GUARD(l, "re_lighting_read_pixels")
+
+// the device buffers of the from-world path, allocated on first use; the directional slots grow with max_directional_lights (the previous set is kept)
+static int world_buffers(re_lighting *l, uint32_t max_dir, uint32_t nl) {
+    auto grow = [&](uint32_t **p, size_t words, size_t keep) -> hipError_t {
+        uint32_t *q = nullptr; hipError_t e = hipMalloc(reinterpret_cast<void **>(&q), words * 4);
+        if (e != hipSuccess) return e;
+        if (keep && *p) { e = hipMemcpy(q, *p, keep * 4, hipMemcpyDeviceToDevice); if (e != hipSuccess) { (void)hipFree(q); return e; } }
+        (void)hipFree(*p); *p = q; return hipSuccess;
+    };
+    if (!l->d_sel) {
+        LCHK(l, hipMalloc(reinterpret_cast<void **>(&l->d_sel), sizeof(WorldSel))); LCHK(l, hipMemset(l->d_sel, 0, sizeof(WorldSel)));
+        LCHK(l, hipMalloc(reinterpret_cast<void **>(&l->d_params), sizeof(LightParams)));
+        LCHK(l, hipMalloc(reinterpret_cast<void **>(&l->d_place), ((size_t)l->cfg.max_spot_lights + 1) * 4));
+        LCHK(l, hipEventCreateWithFlags(&l->ev_world, hipEventDisableTiming));
+        const uint32_t caps[3] = { 0, l->cfg.max_point_lights, l->cfg.max_spot_lights };
+        for (int t = 1; t < 3; t++) {
+            const size_t w = (size_t)caps[t] + 1;
+            LCHK(l, grow(&l->d_prev[t], w, 0)); LCHK(l, grow(&l->d_stage[t], w, 0)); LCHK(l, grow(&l->d_slot_li[t], w, 0)); LCHK(l, grow(&l->d_slot_id[t], w, 0));
+            l->cap[t] = caps[t];
+        }
+    }
+    if (!l->d_prev[0] || max_dir > l->cap[0]) {
+        const size_t w = (size_t)max_dir + 1;
+        LCHK(l, grow(&l->d_prev[0], w, l->d_prev[0] ? (size_t)l->cap[0] : 0)); LCHK(l, grow(&l->d_stage[0], w, 0)); LCHK(l, grow(&l->d_slot_li[0], w, 0)); LCHK(l, grow(&l->d_slot_id[0], w, 0));
+        l->cap[0] = max_dir;
+    }
+    if (nl > l->lmask_cap || !l->d_lmask) { (void)hipFree(l->d_lmask); l->d_lmask = nullptr; LCHK(l, hipMalloc(reinterpret_cast<void **>(&l->d_lmask), ((size_t)nl + 1) * 4)); l->lmask_cap = nl; }
+    return RE_OK;
+}
+
+extern "C" int re_lighting_set_lights_from_world(re_lighting *l, re_ctx *c, const re_camera *cam, const re_world_light_args *a, re_world_lights *out) try {
+    if (!l) return RE_E_ARG;
+    if (!c || !cam || !a) return l->fail(RE_E_ARG, "re_lighting_set_lights_from_world: NULL argument");
+    // what each type unwraps besides get_ref::<LightInformation>: direction (directional, :700-720), direction, fov, cutoff and outer cutoff (point, :752-780)
+    static const uint32_t need[3] = { re::LI_HAS | RE_LI_DIRECTION, re::LI_HAS | RE_LI_CUTOFF | RE_LI_OUTER_CUTOFF | RE_LI_DIRECTION | RE_LI_FOV, re::LI_HAS };
+    re::WorldLightsView V;
+    { const int rc = re::world_lights_view(c, l->cfg.device, cam, need, &V, &l->err); if (rc != RE_OK) return rc; }
+    LCHK(l, hipSetDevice(l->cfg.device));
+    { const int rc = world_buffers(l, a->max_directional_lights, V.nl); if (rc != RE_OK) return rc; }
+    const uint32_t maxs[3] = { a->max_directional_lights, l->cfg.max_point_lights, l->cfg.max_spot_lights };
+    WorldSelArgs S{};
+    S.nl = V.nl; S.rows = V.light_rows; S.flags = V.flags; S.row_id = V.row_id; S.row_cell = V.row_cell; S.cell_key = V.cell_key; S.cell_flags = V.cell_flags; S.sh_cells = V.sh_cells;
+    S.info = V.info; S.lmask = l->d_lmask; S.sel = l->d_sel;
+    for (int t = 0; t < 3; t++) { S.max[t] = maxs[t]; S.need[t] = need[t]; S.prev[t] = l->d_prev[t]; S.stage[t] = l->d_stage[t]; S.slot_li[t] = l->d_slot_li[t]; S.slot_id[t] = l->d_slot_id[t]; }
+    hipLaunchKernelGGL(k_world_select, dim3(1), dim3(SEL_THREADS), 0, V.stream, S, V.Q);
+    LCHK(l, hipGetLastError());
+    WorldSel h{};
+    if (!(V.complete[0] && V.complete[1] && V.complete[2])) {                 // some light lacks what its type unwraps: is one of them selected?
+        LCHK(l, hipMemcpyAsync(&h, l->d_sel, sizeof h, hipMemcpyDeviceToHost, V.stream)); LCHK(l, hipStreamSynchronize(V.stream));
+        if (h.bad_id != 0xFFFFFFFFu)
+            return l->fail(RE_E_STATE, "re_lighting_set_lights_from_world: light entity %u is selected but lacks LightInformation or a field its type unwraps (the reference panics)", h.bad_id);
+    }
+    if (!l->dev_params) LCHK(l, hipMemcpyAsync(l->d_params, &l->P, sizeof(LightParams), hipMemcpyHostToDevice, V.stream));   // a type without nearby lights keeps what set_lights uploaded
+    WorldCommitArgs W{};
+    W.sel = l->d_sel; W.rows = V.light_rows; W.pos = V.pos; W.info = V.info; W.max_spot = l->cfg.max_spot_lights;
+    for (int t = 0; t < 3; t++) { W.slot_li[t] = l->d_slot_li[t]; W.stage[t] = l->d_stage[t]; W.prev[t] = l->d_prev[t]; W.cam[t] = cam->position[t]; }
+    W.cutoff = a->no_light_source_cutoff; W.default_diffuse = a->default_diffuse_factor;
+    W.spot = l->d_spot; W.slab = l->d_slab; W.point = l->d_point; W.params = l->d_params; W.place = l->d_place;
+    hipLaunchKernelGGL(k_world_commit, dim3(1), dim3(WL_THREADS), 0, V.stream, W);
+    LCHK(l, hipGetLastError());
+    LCHK(l, hipEventRecord(l->ev_world, V.stream));
+    LCHK(l, hipStreamWaitEvent(l->stream, l->ev_world, 0));                   // re_lighting_run is ordered behind the upload
+    l->dev_params = true;
+    if (out) {
+        LCHK(l, hipMemcpyAsync(&h, l->d_sel, sizeof h, hipMemcpyDeviceToHost, V.stream)); LCHK(l, hipStreamSynchronize(V.stream));
+        out->any_light_source_visible = (h.n_nearby[0] || h.n_nearby[1] || h.n_nearby[2]) ? 1u : 0u;
+        for (int t = 0; t < 3; t++) {
+            out->n_nearby[t] = h.n_nearby[t]; out->n_slots[t] = h.n_slots[t];
+            l->h_slot_ids[t].resize(h.n_slots[t]);
+            if (h.n_slots[t]) LCHK(l, hipMemcpy(l->h_slot_ids[t].data(), l->d_slot_id[t], (size_t)h.n_slots[t] * 4, hipMemcpyDeviceToHost));
+            out->slot_ids[t] = h.n_slots[t] ? l->h_slot_ids[t].data() : nullptr;
+        }
+    }
+    return RE_OK;
+} RE_ABI_GUARD(l, "re_lighting_set_lights_from_world")

@@ -93,6 +93,21 @@ class DeferredLighting:
         keep = []; S = fill_lights_struct(_capi.Lights(), L, keep)
         self._check(self._L.re_lighting_set_lights(self._h, C.byref(S)), "re_lighting_set_lights")
 
+    def set_lights_from_world(self, pipeline, camera, max_directional_lights, no_light_source_cutoff=0.2, default_diffuse_factor=0.2, wait=True):
+        """the three upload_*_lights of RenderSystem::draw from the pipeline's world (re_lighting_set_lights_from_world).  wait=True returns
+        dict(any_light_source_visible, n_nearby, n_slots, slot_ids), each per type in the order (directional, point, spot); wait=False returns None
+        and leaves the upload in flight behind the pipeline's stream"""
+        cam = camera if isinstance(camera, _capi.CameraC) else camera.to_c()
+        args = _capi.WorldLightArgs(max_directional_lights, no_light_source_cutoff, default_diffuse_factor)
+        out = _capi.WorldLights() if wait else None
+        self._check(self._L.re_lighting_set_lights_from_world(self._h, pipeline._h, C.byref(cam), C.byref(args), C.byref(out) if wait else None),
+                    "re_lighting_set_lights_from_world")
+        if not wait:
+            return None
+        ids = [np.ctypeslib.as_array(out.slot_ids[t], (out.n_slots[t],)).copy() if out.n_slots[t] else np.zeros(0, np.uint32) for t in range(3)]
+        return dict(any_light_source_visible=bool(out.any_light_source_visible), n_nearby=[int(x) for x in out.n_nearby],
+                    n_slots=[int(x) for x in out.n_slots], slot_ids=ids)
+
     def run(self):
         us = C.c_float()
         self._check(self._L.re_lighting_run(self._h, C.byref(us)), "re_lighting_run")

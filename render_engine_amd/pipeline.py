@@ -79,6 +79,9 @@ def create_level_of_views(render_distance):
     return np.array([0.0, v1, v2, v3, v4], np.float32), np.array([v1, v2, v3, v4, v5], np.float32)
 
 
+# re_light_information (LightInformation, exports/light_components.rs:11-24): present = RE_LI_* bits of the Option fields that are Some
+LIGHT_INFORMATION_DT = np.dtype([("radius", "f4"), ("diffuse", "f4", (3,)), ("specular", "f4", (3,)), ("ambient", "f4", (4,)), ("linear", "f4"), ("quadratic", "f4"),
+                                 ("cutoff", "f4"), ("outer_cutoff", "f4"), ("direction", "f4", (3,)), ("fov", "f4"), ("present", "u4")])
 CHANGE_DT = np.dtype([("kind", "u4"), ("entity_id", "u4"), ("component", "u4"), ("reserved", "u4"), ("value", "f4", (4,))])   # re_change
 
 
@@ -443,6 +446,24 @@ class Pipeline:
         b = C.c_uint32()
         self._check(self._L.re_ecs_bitset(self._h, entity_id, C.byref(b)), "re_ecs_bitset")
         return b.value
+
+    def set_light_information(self, ids, infos):
+        """ECS::write_component::<LightInformation> for each id (infos: LIGHT_INFORMATION_DT records, one per id); infos=None removes the component"""
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        if infos is None:
+            ptr = None
+        else:
+            infos = np.ascontiguousarray(infos, LIGHT_INFORMATION_DT).reshape(-1)
+            if len(infos) != len(ids):
+                raise ValueError("one LightInformation record per entity id")
+            ptr = infos.ctypes.data
+        self._check(self._L.re_set_light_information(self._h, ids.ctypes.data, len(ids), ptr), "re_set_light_information")
+
+    def light_information(self, eid):
+        """the LightInformation record of one entity (re_read_component(RE_C_LIGHT_INFORMATION)); RenderEngineError when it carries none"""
+        v = np.zeros(1, LIGHT_INFORMATION_DT)
+        self._check(self._L.re_read_component(self._h, int(eid), _capi.C_LIGHT_INFORMATION, v.ctypes.data), "re_read_component")
+        return v[0]
 
     def visible_lights(self, cam, light_type, capacity=65536):
         """ids (ascending) of the lights of one type (F_LIGHT_*) RenderFlow::render finds near the camera: flows/shadow_flow.rs:455-513"""
