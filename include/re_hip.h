@@ -508,6 +508,60 @@ typedef struct {
 } re_world_lights;
 int re_lighting_set_lights_from_world(re_lighting *l, re_ctx *ctx, const re_camera *cam, const re_world_light_args *args, re_world_lights *out /* nullable */);
 
+/* ---- shadow flow: ShadowFlow::calculate_shadow_maps (flows/shadow_flow.rs:111-453), called by RenderFlow::render (flows/render_flow.rs:247-263) ----
+ * The round-robin scheduler that decides, once per frame, whether a light gets a new shadow map: servicing type Directional -> Point -> Spot with an
+ * Option<EntityId>, a queue of free texture indexes (0..n_shadow_maps, ShadowFlow::new(6) in render_flow.rs:240), the point / spot maps and the spot
+ * lights' upload lists (upload_matrices / upload_view_matrices / upload_indexes).  All of it lives in device memory; re_shadow_step is one
+ * single-workgroup launch on the world context's stream, behind the work already enqueued there.
+ *   inputs:    the nearby lights of the type (re_visible_lights(cam, type)), the lighting context's previous sets (RenderFlow's visible_*_lights: what
+ *              upload_*_lights of the frame before took; l == NULL: empty sets), live positions and LightInformation.  Hash order -> ascending EntityId.
+ *   directional: the candidates are the live entities with sortable index 1 (ecs.get_entities_with_sortable()[1], :156), not the light flags; the first
+ *              one is taken and, as directional_lights is never filled, pops a free index every frame -- the frame that finds the queue empty returns
+ *              RE_E_STATE naming the light where the reference panics (:173).  The light camera is orthographic with left = right = top = bottom =
+ *              outline_length (its projection divides by zero; nothing reads it).
+ *   point:     find_next_light_to_have_shadow_map runs while the servicing light is None; Point(Some(id)) then pops one index per frame until the queue is
+ *              empty and stays (the indexes are not recorded, so they never come back).  Camera: fov of the light, aspect window_width / window_height.
+ *   spot:      up to six faces, one per frame (direction / up tables of :300-320), CameraBuilder((1024, 1024)), fov 90, near 0.10, far = radius; the
+ *              light's projection * view is the culler and is appended to the upload lists with its view matrix and index; after six faces Directional(None).
+ *   culler:    for directional and point maps the MAIN camera's projection_view (:192, :248); for spot maps the light matrix.  box = the frustum_aabb
+ *              candidate box of the light camera (visible_world_flow.rs:117-129: position, far = radius, direction).
+ * A frame calls re_shadow_step BEFORE re_lighting_set_lights_from_world (render() runs calculate_shadow_maps before draw uploads the lights), so the
+ * step sees the previous frame's sets.
+ * out (nullable) receives the decision (host memory).  With out == NULL the call does not wait for the device unless a check is needed: some point /
+ * spot light lacks what its path unwraps, a light of the world was removed, or a directional candidate has been seen (re_shadow_stats.n_host_waits).
+ * Errors: ctx and l on different devices (RE_E_ARG), no world (RE_E_STATE), a ctx with a shard range (RE_E_UNSUPPORTED), a chosen light that is gone or
+ * lacks LightInformation or what its path unwraps -- direction for directional lights, direction and fov for point lights -- or a directional light
+ * with no free index (RE_E_STATE, naming the entity; the shadow state is left unchanged).
+ * Scope: this is the scheduler half of the shadow flow.  The light view itself -- the frustum-only visibility query and the instance pack into the
+ * shadow render system with its own static cache (render_flow.rs:267-309, 352-542) -- is not provided yet; the frame carries the culler planes,
+ * candidate box, position and far distance that query will take. */
+typedef struct re_shadow re_shadow;
+typedef struct { uint32_t n_shadow_maps /* 6 in the reference; 1..32 */, upload_capacity /* entries of the upload lists kept on the device (0 = 64) */; } re_shadow_config;
+int         re_shadow_create(re_ctx *ctx, const re_shadow_config *cfg, re_shadow **out);
+void        re_shadow_destroy(re_shadow *s);
+const char *re_shadow_last_error(const re_shadow *s);   /* s may be NULL: the error of the last failed re_shadow_create */
+typedef struct { uint32_t window_width, window_height; } re_shadow_args;   /* the main camera's window: aspect of point-light cameras */
+typedef struct {
+    uint32_t new_map;                   /* NewMapRequired */
+    uint32_t light_type;                /* RE_WL_* of the handler that ran this frame */
+    uint32_t entity_id;                 /* the light (0xFFFFFFFF without a map) */
+    uint32_t face;                      /* spot maps: 0..5; otherwise 0xFFFFFFFF */
+    uint32_t texture_index;             /* TextureArrayIndex (0xFFFFFFFF without a map) */
+    uint32_t n_uploads;                 /* length of the upload lists so far */
+    float light_projection_view[16];    /* the light camera's projection * view, column-major */
+    float light_view[16];
+    float culler[16];                   /* the projection * view whose planes cull the light view */
+    float planes[24];                   /* RenderFrustumCuller::new(culler) (render_frustum_culler.rs:59-78) */
+    float box[6];                       /* frustum_aabb candidate box: xmin, xmax, ymin, ymax, zmin, zmax */
+    float position[3], far_draw;        /* light camera position and far draw distance (= radius): LOD and distance origin of the light view */
+} re_shadow_frame;                      /* 352 bytes; all zero past n_uploads when new_map == 0 */
+typedef struct { uint32_t n_steps, n_host_waits, n_column_uploads; } re_shadow_stats;
+int re_shadow_step(re_shadow *s, re_lighting *l /* nullable */, const re_camera *cam, const re_shadow_args *args, uint32_t flags /* reserved: must be 0, else RE_E_ARG */,
+                   re_shadow_frame *out /* nullable */);
+/* the LAST min(n, capacity, upload_capacity) entries of the upload lists, oldest first (the reference's lists grow without bound); waits for the stream */
+int re_shadow_uploads(re_shadow *s, float *matrices, float *view_matrices, uint32_t *indexes, uint32_t capacity, uint32_t *n);
+int re_shadow_get_stats(re_shadow *s, re_shadow_stats *out);
+
 /* ---- history / replay wire format ----
  * The per-frame FrameChange records of the history thread (threads/public_common_structures.rs:7-16), written with bincode 1.3 as
  * threads/history_thread.rs:150-205 does: gameplay_history.txt = bincode(ECS) | bincode(BoundingBoxTree) | bincode(FrameChange)*, and

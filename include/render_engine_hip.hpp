@@ -95,6 +95,7 @@ inline std::vector<LevelOfView> create_level_of_views(float render_distance) {  
 
 class Camera {
   public:
+    std::pair<int, int> get_window_dimensions() const { return window_; }
     Mat4 get_projection_matrix() const { return detail::perspective((float)window_.first / (float)window_.second, fov_, near_, far_); }
     Mat4 get_view_matrix() const { return detail::look_at(position_, TVec3{ position_.x + direction_.x, position_.y + direction_.y, position_.z + direction_.z }, TVec3{ 0, 1, 0 }); }
     TVec3 get_position() const { return position_; } TVec3 get_direction() const { return direction_; }
@@ -322,6 +323,18 @@ class Pipeline {
     void write_light_information(EntityId e, const re_light_information &info) { upload_if_needed(); check(re_set_light_information(ctx_, &e, 1u, &info), "re_set_light_information"); }
     void remove_light_information(EntityId e) { upload_if_needed(); check(re_set_light_information(ctx_, &e, 1u, nullptr), "re_set_light_information"); }
     re_light_information get_light_information(EntityId e) { re_light_information v{}; read(e, RE_C_LIGHT_INFORMATION, &v); return v; }
+    // ShadowFlow::calculate_shadow_maps (flows/shadow_flow.rs:111-453): one step of the shadow scheduler of `shadow` (re_shadow_create on this world),
+    // called before upload_lights in a frame; out (nullable) receives the decision
+    void calculate_shadow_maps(re_shadow *shadow, re_lighting *lighting, const Camera &camera, re_shadow_frame *out = nullptr) {
+        upload_if_needed();
+        re_camera cam{}; const TVec3 cp = camera.get_position();
+        cam.position[0] = cp.x; cam.position[1] = cp.y; cam.position[2] = cp.z; cam.far_draw = camera.get_far_draw_distance();
+        const Mat4 pv = detail::mul(camera.get_projection_matrix(), camera.get_view_matrix());
+        std::memcpy(cam.projection_view, pv.data(), 64);
+        const re_shadow_args args{ (uint32_t)camera.get_window_dimensions().first, (uint32_t)camera.get_window_dimensions().second };
+        const int rc = re_shadow_step(shadow, lighting, &cam, &args, 0u, out);
+        if (rc != RE_OK) throw std::runtime_error(std::string("re_shadow_step: ") + re_shadow_last_error(shadow));
+    }
     // RenderSystem::draw's upload_{directional,point,spot}_lights (render_system/render_system.rs:563-576, 681-845) into one render system's lighting context
     // (which keeps that render system's previous sets); out (nullable) receives the slot ids per type and anyLightSourceVisible
     void upload_lights(re_lighting *lighting, const Camera &camera, uint32_t max_directional_lights, float no_light_source_cutoff, float default_diffuse_factor,

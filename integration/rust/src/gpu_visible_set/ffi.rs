@@ -39,6 +39,12 @@ use std::os::raw::{c_char, c_int, c_void};
     pub quadratic: f32, pub cutoff: f32, pub outer_cutoff: f32, pub direction: [f32; 3], pub fov: f32, pub present: u32 }   // 80 bytes
 #[repr(C)] pub struct ReWorldLightArgs { pub max_directional_lights: u32, pub no_light_source_cutoff: f32, pub default_diffuse_factor: f32 }
 #[repr(C)] pub struct ReWorldLights { pub any_light_source_visible: u32, pub n_nearby: [u32; 3], pub n_slots: [u32; 3], pub slot_ids: [*const u32; 3] }
+#[repr(C)] pub struct ReShadow { _p: [u8; 0] }
+#[repr(C)] pub struct ReShadowConfig { pub n_shadow_maps: u32, pub upload_capacity: u32 }
+#[repr(C)] pub struct ReShadowArgs { pub window_width: u32, pub window_height: u32 }
+#[repr(C)] #[derive(Copy, Clone)] pub struct ReShadowFrame { pub new_map: u32, pub light_type: u32, pub entity_id: u32, pub face: u32, pub texture_index: u32, pub n_uploads: u32,
+    pub light_projection_view: [f32; 16], pub light_view: [f32; 16], pub culler: [f32; 16], pub planes: [f32; 24], pub box_: [f32; 6], pub position: [f32; 3], pub far_draw: f32 }   // 352 bytes
+#[repr(C)] #[derive(Copy, Clone, Default)] pub struct ReShadowStats { pub n_steps: u32, pub n_host_waits: u32, pub n_column_uploads: u32 }
 #[repr(C)] pub struct ReHistory { _private: [u8; 0] }
 #[repr(C)] pub struct ReTypeIds { pub position: u64, pub rotation: u64, pub scale: u64, pub velocity: u64, pub acceleration: u64, pub rotation_velocity: u64,
                                   pub rotation_acceleration: u64, pub has_moved: u64, pub has_rotated: u64 }
@@ -104,6 +110,12 @@ extern "C" {
     pub fn re_lighting_read(l: *mut ReLighting, out_rgba: *mut f32) -> c_int;
     pub fn re_lighting_read_pixels(l: *mut ReLighting, pixel_index: *const u32, n: u32, out_rgba: *mut f32) -> c_int;
     pub fn re_lighting_set_lights_from_world(l: *mut ReLighting, ctx: *mut ReCtx, cam: *const ReCamera, args: *const ReWorldLightArgs, out: *mut ReWorldLights) -> c_int;
+    pub fn re_shadow_create(ctx: *mut ReCtx, cfg: *const ReShadowConfig, out: *mut *mut ReShadow) -> c_int;
+    pub fn re_shadow_destroy(s: *mut ReShadow);
+    pub fn re_shadow_last_error(s: *const ReShadow) -> *const c_char;
+    pub fn re_shadow_step(s: *mut ReShadow, l: *mut ReLighting, cam: *const ReCamera, args: *const ReShadowArgs, flags: u32, out: *mut ReShadowFrame) -> c_int;
+    pub fn re_shadow_uploads(s: *mut ReShadow, matrices: *mut f32, view_matrices: *mut f32, indexes: *mut u32, capacity: u32, n: *mut u32) -> c_int;
+    pub fn re_shadow_get_stats(s: *mut ReShadow, out: *mut ReShadowStats) -> c_int;
     pub fn re_history_create(ids: *const ReTypeIds, flags: u32, out: *mut *mut ReHistory) -> c_int;
     pub fn re_history_destroy(h: *mut ReHistory);
     pub fn re_history_last_error(h: *const ReHistory) -> *const c_char;

@@ -164,6 +164,21 @@ impl GpuVisibleSet {
         self.check(unsafe { re_set_light_information(self.ctx, ids.as_ptr(), ids.len() as u32, p) })
     }
 
+    /// ShadowFlow::calculate_shadow_maps (flows/shadow_flow.rs:111-453) on the device, before set_lights_from_world in a frame.  `shadow` comes from
+    /// re_shadow_create on this world.  Returns the frame's decision (new_map == 0: NoNewMapRequired).
+    pub fn calculate_shadow_maps(&mut self, shadow: *mut ReShadow, lighting: *mut ReLighting, projection_view: &[f32; 16], position: [f32; 3], direction: [f32; 3],
+                                 far_draw: f32, window: (u32, u32)) -> Result<ReShadowFrame, GpuError> {
+        let cam = ReCamera { projection_view: *projection_view, position, direction, far_draw, n_lod: 0, lod_min: [0.0; 8], lod_max: [0.0; 8] };
+        let args = ReShadowArgs { window_width: window.0, window_height: window.1 };
+        let mut out = MaybeUninit::<ReShadowFrame>::zeroed();
+        let rc = unsafe { re_shadow_step(shadow, lighting, &cam, &args, 0, out.as_mut_ptr()) };
+        if rc != RE_OK {
+            let p = unsafe { re_shadow_last_error(shadow) };
+            return Err(GpuError { code: rc, message: if p.is_null() { String::new() } else { unsafe { CStr::from_ptr(p) }.to_string_lossy().into_owned() } });
+        }
+        Ok(unsafe { out.assume_init() })
+    }
+
     /// RenderSystem::upload_{directional,point,spot}_lights of one render system's draw (render_system.rs:563-576) from this world into its lighting
     /// context: the previous sets live in `lighting`.  Returns the slot ids per type (directional, point, spot; None = that type's arrays were kept) and
     /// anyLightSourceVisible.

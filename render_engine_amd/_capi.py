@@ -123,6 +123,25 @@ class WorldLights(C.Structure):
     _fields_ = [("any_light_source_visible", C.c_uint32), ("n_nearby", C.c_uint32 * 3), ("n_slots", C.c_uint32 * 3), ("slot_ids", C.POINTER(C.c_uint32) * 3)]
 
 
+# the shadow flow (re_shadow_*: ShadowFlow::calculate_shadow_maps on the device)
+class ShadowConfig(C.Structure):
+    _fields_ = [("n_shadow_maps", C.c_uint32), ("upload_capacity", C.c_uint32)]
+
+
+class ShadowArgs(C.Structure):
+    _fields_ = [("window_width", C.c_uint32), ("window_height", C.c_uint32)]
+
+
+class ShadowFrame(C.Structure):
+    _fields_ = [("new_map", C.c_uint32), ("light_type", C.c_uint32), ("entity_id", C.c_uint32), ("face", C.c_uint32), ("texture_index", C.c_uint32),
+                ("n_uploads", C.c_uint32), ("light_projection_view", C.c_float * 16), ("light_view", C.c_float * 16), ("culler", C.c_float * 16),
+                ("planes", C.c_float * 24), ("box", C.c_float * 6), ("position", C.c_float * 3), ("far_draw", C.c_float)]
+
+
+class ShadowStats(C.Structure):
+    _fields_ = [("n_steps", C.c_uint32), ("n_host_waits", C.c_uint32), ("n_column_uploads", C.c_uint32)]
+
+
 # every symbol include/re_hip.h declares
 EXPORTS = ["re_create", "re_destroy", "re_last_error", "re_abi_version", "re_upload_entities", "re_set_model_lod", "re_cull_pack", "re_tick",
            "re_apply_changes", "re_apply_changes_ex", "re_add_entities", "re_set_shard_range", "re_list_migrants", "re_export_entities", "re_collide", "re_wait", "re_run_frames", "re_comm_unique_id", "re_comm_init", "re_comm_adopt", "re_comm_destroy", "re_allgather_visible", "re_gather_wait", "re_copy_visible", "re_set_output_buffers", "re_set_output_count", "re_read_component", "re_set_light_information", "re_ecs_bitset", "re_ecs_query", "re_visible_lights", "re_section_keys", "re_get_out_of_bounds", "re_get_stats",
@@ -130,6 +149,7 @@ EXPORTS = ["re_create", "re_destroy", "re_last_error", "re_abi_version", "re_upl
            "re_timing_begin", "re_timing_collect", "re_get_last_candidates", "re_debug_get_plan_stats",
            "re_lighting_create", "re_lighting_destroy", "re_lighting_last_error", "re_lighting_upload_gbuffer", "re_lighting_set_lights",
            "re_lighting_run", "re_lighting_read", "re_lighting_read_pixels", "re_lighting_set_lights_from_world",
+           "re_shadow_create", "re_shadow_destroy", "re_shadow_last_error", "re_shadow_step", "re_shadow_uploads", "re_shadow_get_stats",
            "re_history_create", "re_history_destroy", "re_history_last_error", "re_history_set_state", "re_history_get_state", "re_history_record",
            "re_history_count", "re_history_get", "re_history_encode", "re_history_write", "re_history_load"]
 
@@ -216,6 +236,12 @@ def load():
     L.re_lighting_read_pixels.restype = C.c_int; L.re_lighting_read_pixels.argtypes = [vp, vp, C.c_uint32, vp]
     L.re_lighting_set_lights_from_world.restype = C.c_int
     L.re_lighting_set_lights_from_world.argtypes = [vp, vp, C.POINTER(CameraC), C.POINTER(WorldLightArgs), C.POINTER(WorldLights)]
+    L.re_shadow_create.restype = C.c_int; L.re_shadow_create.argtypes = [vp, C.POINTER(ShadowConfig), C.POINTER(vp)]
+    L.re_shadow_destroy.restype = None; L.re_shadow_destroy.argtypes = [vp]
+    L.re_shadow_last_error.restype = C.c_char_p; L.re_shadow_last_error.argtypes = [vp]
+    L.re_shadow_step.restype = C.c_int; L.re_shadow_step.argtypes = [vp, vp, C.POINTER(CameraC), C.POINTER(ShadowArgs), C.c_uint32, C.POINTER(ShadowFrame)]
+    L.re_shadow_uploads.restype = C.c_int; L.re_shadow_uploads.argtypes = [vp, vp, vp, vp, C.c_uint32, _u32p]
+    L.re_shadow_get_stats.restype = C.c_int; L.re_shadow_get_stats.argtypes = [vp, C.POINTER(ShadowStats)]
     L.re_history_create.restype = C.c_int; L.re_history_create.argtypes = [C.POINTER(TypeIds), C.c_uint32, C.POINTER(vp)]
     L.re_history_destroy.restype = None; L.re_history_destroy.argtypes = [vp]
     L.re_history_last_error.restype = C.c_char_p; L.re_history_last_error.argtypes = [vp]

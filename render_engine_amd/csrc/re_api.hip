@@ -241,6 +241,7 @@ struct re_ctx {
     std::vector<uint32_t> h_light_rows; DevBuf<uint32_t> d_light_rows, d_light_out; bool light_rows_dirty = true;   // rows that carry a FindLightType (members of their section's light set); ascending EntityId on the device
     // LightInformation (re_set_light_information) by row: the host copy is the truth (nothing on the device writes it); the device column d_li follows the light list
     std::unordered_map<uint32_t, re_light_information> h_li; std::vector<re_light_information> h_li_col; DevBuf<re_light_information> d_li; bool li_dirty = true; bool li_complete[3] = {};
+    uint64_t li_epoch = 0, rows_epoch = 0;             // bumped when the LightInformation column is rebuilt / when rows may have been added, removed or regrouped (shadow flow caches)
     std::vector<hipEvent_t> k1_events; uint32_t k1_used = 0, k1_every = 1, k1_seen = 0, k1_kind = 0; bool k1_timing = false;   // per-launch timing of one kernel (re_timing_begin): k_scan_cull, k_tick or k_pack_large
 
     int fail(int code, const char *fmt, ...) {
@@ -707,6 +708,7 @@ static int upload_lod_tables(re_ctx *c) {
 }
 
 extern "C" int re_upload_entities(re_ctx *c, const re_entities *E, uint32_t *n_rejected) try {
+    if (c) c->rows_epoch++;
     if (!c) return RE_E_ARG;
     if (!E || (E->n && (!E->entity_id || !E->model_index || !E->flags || !E->original_aabb || !E->position))) return c->fail(RE_E_ARG, "re_upload_entities: missing required array");
     HIPCHK(c, hipSetDevice(c->device));
@@ -2447,6 +2449,7 @@ static int rebucket(re_ctx *c, uint32_t n_movers, const std::vector<TreeOp> *pre
 
 // rows the last tick / change batch removed because they left the world: mirror RE_F_DEAD on the host
 static int absorb_out_of_bounds(re_ctx *c, uint32_t n_oob) {
+    if (c) c->rows_epoch++;
     uint32_t cnt = std::min(n_oob, c->list_cap);
     if (!cnt) return RE_OK;
     { int src = sync_mirrors(c); if (src != RE_OK) return src; }
@@ -2734,6 +2737,7 @@ static int regrow_groups(re_ctx *c) {
 // section decision on the device (the upload's kernel over the new row range), host mirrors extended; the tree does not know them yet (add_keys).
 struct NewRow { uint32_t src, row; };
 static int create_rows(re_ctx *c, const re_entities *E, const std::vector<NewRow> &rows, uint32_t *n_rejected) {
+    if (c) c->rows_epoch++;
     const uint32_t m = (uint32_t)rows.size(), row0 = c->n;
     if (n_rejected) *n_rejected = 0;
     if (!m) return RE_OK;
@@ -2821,6 +2825,7 @@ static int create_rows(re_ctx *c, const re_entities *E, const std::vector<NewRow
 // in_frame: the batch belongs to a frame's logic phase (apply_change); false: Pipeline::register_model_instances between frames (re_add_entities) -- the
 // changed-static set then survives until the next render, which re-caches those sections.
 static int apply_changes_impl(re_ctx *c, const re_change *changes, uint32_t n, const re_entities *added, re_tick_result *out, bool in_frame) {
+    if (c) c->rows_epoch++;
     if (!c->h_res) return c->fail(RE_E_STATE, "re_apply_changes: no world uploaded");
     if (n && !changes) return c->fail(RE_E_ARG, "re_apply_changes: changes is NULL");
     if (in_frame && !c->have_cull) return c->fail(RE_E_STATE, "re_apply_changes: apply_change runs inside a frame, after its render (flows/pipeline.rs:212-271); call re_cull_pack first");
@@ -3690,13 +3695,13 @@ extern "C" int re_set_light_information(re_ctx *c, const uint32_t *entity_ids, u
 } RE_ABI_GUARD(c, "re_set_light_information")
 
 // what re_lighting_set_lights_from_world needs of the world (re_world_lights.h)
-int re::world_lights_view(re_ctx *c, int device, const re_camera *cam, const uint32_t need[3], WorldLightsView *v, std::string *err) {
-    auto fail = [&](int code, const char *msg) { *err = msg; return code; };
-    if (c->device != device) return fail(RE_E_ARG, "re_lighting_set_lights_from_world: the world context and the lighting context are on different devices");
-    if (!c->h_res) return fail(RE_E_STATE, "re_lighting_set_lights_from_world: no world uploaded");
-    if (c->shard_hi) return fail(RE_E_UNSUPPORTED, "re_lighting_set_lights_from_world: the context holds a shard of the world (re_set_shard_range): it sees only its own lights");
+int re::world_lights_view(re_ctx *c, int device, const re_camera *cam, const uint32_t need[3], WorldLightsView *v, std::string *err, const char *who) {
+    auto fail = [&](int code, const char *msg) { *err = std::string(who) + ": " + msg; return code; };
+    if (c->device != device) return fail(RE_E_ARG, "the world context and the lighting context are on different devices");
+    if (!c->h_res) return fail(RE_E_STATE, "no world uploaded");
+    if (c->shard_hi) return fail(RE_E_UNSUPPORTED, "the context holds a shard of the world (re_set_shard_range): it sees only its own lights");
     auto ctx_fail = [&](int rc) { *err = c->err; return rc; };
-    if (hipSetDevice(c->device) != hipSuccess) return fail(RE_E_HIP, "re_lighting_set_lights_from_world: hipSetDevice failed");
+    if (hipSetDevice(c->device) != hipSuccess) return fail(RE_E_HIP, "hipSetDevice failed");
     { int rc_ = resolve(c); if (rc_ != RE_OK) return ctx_fail(rc_); }            // the section table is settled (movers of the last tick are in)
     { int rc_ = sync_light_rows(c); if (rc_ != RE_OK) return ctx_fail(rc_); }
     const uint32_t nl = (uint32_t)c->h_light_rows.size();
@@ -3711,13 +3716,13 @@ int re::world_lights_view(re_ctx *c, int device, const re_camera *cam, const uin
             if (c->h_flags[r] & F_DEAD) continue;
             for (int t = 0; t < 3; t++) if ((c->h_flags[r] & type_bit[t]) && (c->h_li_col[i].present & need[t]) != need[t]) c->li_complete[t] = false;
         }
-        if (c->d_li.n < c->h_li_col.size() && c->d_li.alloc(c->h_li_col.size(), nullptr) != hipSuccess) return fail(RE_E_HIP, "re_lighting_set_lights_from_world: device allocation failed");
-        if (hipMemcpy(c->d_li.p, c->h_li_col.data(), c->h_li_col.size() * sizeof(re_light_information), hipMemcpyHostToDevice) != hipSuccess) return fail(RE_E_HIP, "re_lighting_set_lights_from_world: copy of the LightInformation column failed");
-        c->li_dirty = false;
+        if (c->d_li.n < c->h_li_col.size() && c->d_li.alloc(c->h_li_col.size(), nullptr) != hipSuccess) return fail(RE_E_HIP, "device allocation failed");
+        if (hipMemcpy(c->d_li.p, c->h_li_col.data(), c->h_li_col.size() * sizeof(re_light_information), hipMemcpyHostToDevice) != hipSuccess) return fail(RE_E_HIP, "copy of the LightInformation column failed");
+        c->li_dirty = false; c->li_epoch++;
     }
     v->stream = c->stream; v->nl = nl;
     v->light_rows = c->d_light_rows.p; v->flags = c->d_flags.p; v->row_id = c->d_id.p; v->row_cell = c->d_row_cell.p;
-    v->cell_key = c->d_cell_key.p; v->cell_flags = c->d_cell_flags.p; v->sh_cells = c->d_sh_cells.p; v->pos = c->d_pos.p; v->info = c->d_li.p;
+    v->cell_key = c->d_cell_key.p; v->cell_flags = c->d_cell_flags.p; v->sh_cells = c->d_sh_cells.p; v->pos = c->d_pos.p; v->info = c->d_li.p; v->h_info = c->h_li_col.data(); v->li_epoch = c->li_epoch;
     const float r = cam->far_draw, wsl = (float)c->cfg.atomic_length;
     v->Q = LightQuery{};
     v->Q.culler = Aabb{ cam->position[0] - r, cam->position[0] + r, cam->position[1] - r, cam->position[1] + r, cam->position[2] - r, cam->position[2] + r };
@@ -3727,6 +3732,32 @@ int re::world_lights_view(re_ctx *c, int device, const re_camera *cam, const uin
     for (int t = 0; t < 3; t++) v->complete[t] = c->li_complete[t];
     return RE_OK;
 }
+
+// what the shadow flow needs of the world besides the light view (re_world_lights.h)
+int re::shadow_world(re_ctx *c, ShadowWorld *w, std::string *err) {
+    (void)err;
+    if (w->valid && w->rows_epoch == c->rows_epoch && w->li_epoch == c->li_epoch && w->n_groups == c->h_gkeys.size()) { w->changed = false; return RE_OK; }
+    w->valid = true; w->changed = true; w->rows_epoch = c->rows_epoch; w->li_epoch = c->li_epoch; w->n_groups = (uint32_t)c->h_gkeys.size();
+    w->outline_length = c->cfg.outline_length; w->dead_light = false; w->dir_id.clear(); w->dir_row.clear(); w->dir_info.clear();
+    for (uint32_t r : c->h_light_rows) if (c->h_flags[r] & F_DEAD) { w->dead_light = true; break; }
+    bool any = false;
+    for (const GroupKey &g : c->h_gkeys) if (g.sort == 1) { any = true; break; }
+    if (!any) return RE_OK;                                                     // (the common case: no entity was ever given sortable index 1)
+    std::vector<std::pair<uint32_t, uint32_t>> v;
+    for (uint32_t r = 0; r < c->n; r++)
+        if (!(c->h_flags[r] & (F_DEAD | F_PHANTOM)) && c->h_gclass[r] < c->h_gkeys.size() && c->h_gkeys[c->h_gclass[r]].sort == 1) v.push_back({ c->h_id[r], r });
+    std::sort(v.begin(), v.end());
+    for (auto &p : v) {
+        w->dir_id.push_back(p.first); w->dir_row.push_back(p.second);
+        auto e = c->h_li.find(p.second);
+        re_light_information I{};
+        if (e != c->h_li.end()) { I = e->second; I.present |= LI_HAS; }
+        w->dir_info.push_back(I);
+    }
+    return RE_OK;
+}
+int re::world_device(const re_ctx *c) { return c->device; }
+hipStream_t re::world_stream(const re_ctx *c) { return c->stream; }
 
 // The lights of one type RenderFlow::render finds near the camera (flows/render_flow.rs:249-254 -> flows/shadow_flow.rs:455-513): k_visible_lights over the
 // entities uploaded with RE_F_LIGHT_*.  Stands alone (own visibility test with the AABB culler of radius far_draw); ids in ascending order.

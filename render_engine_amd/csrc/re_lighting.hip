@@ -700,6 +700,13 @@ static int world_buffers(re_lighting *l, uint32_t max_dir, uint32_t nl) {
     return RE_OK;
 }
 
+// the previous sets for the shadow flow (re_world_lights.h)
+void re::lighting_prev(const re_lighting *l, LightingPrev *p) {
+    p->device = l->cfg.device;
+    p->n_prev = l->d_sel ? l->d_sel->n_prev : nullptr;
+    for (int t = 0; t < 3; t++) p->prev[t] = l->d_sel ? l->d_prev[t] : nullptr;
+}
+
 extern "C" int re_lighting_set_lights_from_world(re_lighting *l, re_ctx *c, const re_camera *cam, const re_world_light_args *a, re_world_lights *out) try {
     if (!l) return RE_E_ARG;
     if (!c || !cam || !a) return l->fail(RE_E_ARG, "re_lighting_set_lights_from_world: NULL argument");
