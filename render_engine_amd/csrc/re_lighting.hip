@@ -15,6 +15,12 @@
 //   5. epilogue exactly as main(): (spot + point) + spot -- the spot term is added twice in the shader --, the
 //      default-diffuse floor, clamp.
 // gLightPosition is not read: the shadow value it feeds is computed and discarded by the shader (:105).
+// Contract (tests/test_lighting_exact_gpu.py against the float64 restatement tests/lighting_ref.py):
+//   * exact, as the CPU oracle decides them: the radius cut (sqrtf of the unfused (dx*dx + dy*dy) + dz*dz against the radius; NaN radius = every pixel,
+//     negative radius = none, 0 / -0 = the pixel at the light's exact position), and a light at a pixel's exact position (its ambient part, attenuation 1);
+//     not covered: a distance whose square overflows f32 (|d| >= ~1.8e19: a cone light, or a radius light under a +inf or NaN radius), which gets attenuation 1, not 0;
+//   * within 1e-4 of the float64 value per channel (hardware reciprocals, fused multiply-adds); a channel that close to the default-diffuse cutoff
+//     may take either side of the floor.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <cstdarg>
@@ -54,24 +60,34 @@ __device__ __forceinline__ float3 norm3v(float3 v) { float n = sqrtf(dot3(v, v))
 __device__ __forceinline__ float uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }   // a value every lane holds alike -> a scalar register
 __device__ __forceinline__ float pow64(float x) { x *= x; x *= x; x *= x; x *= x; x *= x; x *= x; return x; }
 
-// one light's contribution to one pixel; A = (pos, radius|unused), B = (diffuse, linear), C = (specular, quadratic), D = ambient rgba
-__device__ __forceinline__ void shade(float3 frag, float3 nrm, float3 od, float3 camdir, float4 A, float4 B, float4 C, float4 D, bool radius_cut, float intensity, float3 &acc) {
+// the oracle's squared distance, (dx*dx + dy*dy) + dz*dz with every operation rounded: what the radius cut is decided on
+__device__ __forceinline__ float d2_unfused(float dx, float dy, float dz) {
+#pragma clang fp contract(off)
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+// a * b, but 0 when either operand is 0 (v_mul_legacy_f32: also 0 * inf and 0 * NaN)
+__device__ __forceinline__ float mul_legacy(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    float r; asm("v_mul_legacy_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));   // (no clang builtin for gfx950)
+    return r;
+#else
+    return a == 0.0f || b == 0.0f ? 0.0f : a * b;
+#endif
+}
+
+// one cone light's contribution to one pixel; A = (pos, unused), B = (diffuse, linear), C = (specular, quadratic), D = ambient rgba
+__device__ __forceinline__ void shade(float3 frag, float3 nrm, float3 od, float3 camdir, float4 A, float4 B, float4 C, float4 D, float intensity, float3 &acc) {
 #pragma clang fp contract(fast)          // this file's arithmetic is tolerance-bound (1e-4), not bit-exact like the cull path: multiply-adds may fuse here (the library is built with -ffp-contract=off)
     // The shader's divisions and square roots are GPU-precision operations in the reference too (GLSL gives no IEEE guarantee); here they are the
     // hardware's reciprocal / reciprocal square root (1 ulp) instead of the ~10-instruction IEEE sequences: the kernel is bound by the VALU work of
     // this function, and the result stays within 1e-6 of the f32 GLSL restatement (tolerance of the path: 1e-4).
     float3 d = sub3(f3(A.x, A.y, A.z), frag);
     const float d2 = dot3(d, d);
-    if (radius_cut) {                                                          // :97-100: dist > radius, decided exactly (the cut is a discontinuity) -- the square root only near the boundary
-        const float r2 = A.w * A.w;
-        if (A.w < 0.0f || d2 > r2 * 1.000001f) return;                         // (a distance is never below a negative radius)
-        const bool shell = d2 > r2 * 0.999999f;
-        if (__builtin_amdgcn_ballot_w64(shell)) {                              // a wave-uniform branch the compiler cannot flatten (the asm pins the operand inside it): flattened,
-            float t = d2; asm volatile("" : "+v"(t));                           // the IEEE square root (22 instructions) ran for every pixel inside the radius
-            if (shell && sqrtf(t) > A.w) return;
-        }
-    }
-    const float inv = __builtin_amdgcn_rsqf(d2), dist = d2 * inv;
+    // a light at the pixel's exact position (d2 = 0): rsq gives +inf, so the direction is NaN and the oracle's fmaxf drops the diffuse and specular parts;
+    // the distance must come out 0 (attenuation 1), not 0 * inf = NaN -- v_mul_legacy_f32 returns 0 when either operand is 0 (as in shade_pair, an
+    // overflowed d2 = +inf then gives attenuation 1 where the oracle's is 0)
+    const float inv = __builtin_amdgcn_rsqf(d2), dist = mul_legacy(d2, inv);
     float3 nd = f3(d.x * inv, d.y * inv, d.z * inv);
     float att = __builtin_amdgcn_rcpf(1.0f + B.w * dist + C.w * dist * dist);  // calculateAttenuation :132-136
     float dc = fmaxf(dot3(nrm, nd), 0.0f);                                     // calculateDiffuse :118-122
@@ -94,18 +110,25 @@ __device__ __forceinline__ f2 max0(f2 v) { f2 r; r.x = fmaxf(v.x, 0.0f); r.y = f
 __device__ __forceinline__ void shade_pair(const PixelPair &X, bool live0, bool live1, float4 A, float4 B, float4 C, float4 D, f2 &ax, f2 &ay, f2 &az) {
 #pragma clang fp contract(fast)
     const f2 dx = A.x - X.fx, dy = A.y - X.fy, dz = A.z - X.fz;
-    const f2 d2 = (dx * dx + dy * dy) + dz * dz;
-    // :97-100: dist > radius, decided exactly (the cut is a discontinuity) -- the square root only near the boundary
+    const f2 d2 = (dx * dx + dy * dy) + dz * dz;                               // (fused: one v_pk_mul, two v_pk_fma)
+    // :97-100: dist > radius, decided exactly as the oracle decides it (the cut is a discontinuity): sqrtf of the UNFUSED d2 against the radius, the square
+    // root only near the boundary.  The fast accept / reject may use the fused d2 above: it is a few ulp from the unfused one, and the margins of 1e-6 are ~8 ulp
     const float r2 = A.w * A.w, r2_out = r2 * 1.000001f, r2_in = r2 * 0.999999f;
     bool in0 = live0 && !(A.w < 0.0f) && !(d2.x > r2_out), in1 = live1 && !(A.w < 0.0f) && !(d2.y > r2_out);      // (a distance is never below a negative radius)
     const bool shell0 = in0 && d2.x > r2_in, shell1 = in1 && d2.y > r2_in;
     if (__builtin_amdgcn_ballot_w64(shell0 || shell1)) {                      // a wave-uniform branch the compiler cannot flatten (the asm pins the operands inside it): flattened,
-        float t0 = d2.x, t1 = d2.y; asm volatile("" : "+v"(t0), "+v"(t1));     // the IEEE square root (22 instructions) ran for every pixel inside the radius
-        if (shell0 && sqrtf(t0) > A.w) in0 = false;
-        if (shell1 && sqrtf(t1) > A.w) in1 = false;
+        float x0 = dx.x, y0 = dy.x, z0 = dz.x, x1 = dx.y, y1 = dy.y, z1 = dz.y;  // the IEEE square root (22 instructions) ran for every pixel inside the radius
+        asm volatile("" : "+v"(x0), "+v"(y0), "+v"(z0), "+v"(x1), "+v"(y1), "+v"(z1));
+        if (shell0 && sqrtf(d2_unfused(x0, y0, z0)) > A.w) in0 = false;
+        if (shell1 && sqrtf(d2_unfused(x1, y1, z1)) > A.w) in1 = false;
     }
     if (!(in0 || in1)) return;
-    const f2 inv = rsq2(d2), dist = d2 * inv;
+    // a light at the pixel's exact position (d2 = 0): the oracle's term is the ambient part with attenuation 1 (its NaN direction is dropped by fmaxf, as
+    // max0 below drops it here); v_mul_legacy_f32 makes the distance 0 there instead of 0 * rsq(0) = 0 * inf = NaN, and is the plain product for every
+    // finite nonzero d2.  (Not for an overflowed d2 = +inf, |d| >= ~1.8e19, which only a +inf or NaN radius admits: rsq gives 0, so the distance is 0 and
+    // the attenuation 1 where the oracle's is 0.)
+    const f2 inv = rsq2(d2);
+    f2 dist; dist.x = mul_legacy(d2.x, inv.x); dist.y = mul_legacy(d2.y, inv.y);
     const f2 ndx = dx * inv, ndy = dy * inv, ndz = dz * inv;
     const f2 att = rcp2(1.0f + B.w * dist + C.w * dist * dist);                // calculateAttenuation :132-136
     const f2 dc = max0((X.nx * ndx + X.ny * ndy) + X.nz * ndz);                // calculateDiffuse :118-122
@@ -224,7 +247,7 @@ __global__ __launch_bounds__(LT_THREADS) void k_deferred_lighting(LightParams Pa
                     const float4 A = Ac[r];
                     float dx = fmaxf(fmaxf(lo[0] - A.x, A.x - hi[0]), 0.0f), dy = fmaxf(fmaxf(lo[1] - A.y, A.y - hi[1]), 0.0f), dz = fmaxf(fmaxf(lo[2] - A.z, A.z - hi[2]), 0.0f);
                     float rr = A.w * 1.00001f + 1e-3f;                              // conservative: the exact per-pixel radius test follows
-                    hit = ((dx * dx + dy * dy) + dz * dz) <= rr * rr;
+                    hit = !(((dx * dx + dy * dy) + dz * dz) > rr * rr);             // (a NaN radius is unbounded: no distance is > NaN in the oracle either)
                 }
                 const uint64_t m = __ballot(hit);
                 if (lane == 0) s_wcnt[wid] = (uint32_t)__popcll(m);
@@ -250,7 +273,7 @@ __global__ __launch_bounds__(LT_THREADS) void k_deferred_lighting(LightParams Pa
                 float3 fn = norm3v(frag[k]);
                 float angle = dot3(sub3(fn, f3(A.x, A.y, A.z)), f3(E.x, E.y, E.z));
                 float intensity = fminf(fmaxf((angle - F.y) / (F.x - F.y), 0.0f), 1.0f);
-                shade(frag[k], nrm[k], od[k], camdir[k], A, B, C, D, false, intensity, point_acc[k]);
+                shade(frag[k], nrm[k], od[k], camdir[k], A, B, C, D, intensity, point_acc[k]);
             }
         }
         float3 spot_acc[NPX];
@@ -456,7 +479,7 @@ __global__ __launch_bounds__(WL_THREADS) void k_world_commit(WorldCommitArgs A) 
         const float v[3] = { a.x, a.y, a.z };
         #pragma unroll
         for (int k = 0; k < 3; k++) { if (v[k] < mn[k]) mn[k] = v[k]; if (v[k] > mx[k]) mx[k] = v[k]; }   // (comparisons: NaN takes no part, as on the host)
-        if (a.w > rm) rm = a.w;
+        if (!(a.w <= rm)) rm = a.w == a.w ? a.w : __builtin_inff();            // (a NaN radius reaches everything: the slab reach becomes unbounded, as on the host)
     }
     for (int d = 32; d >= 1; d >>= 1)
         #pragma unroll
@@ -600,7 +623,8 @@ extern "C" int re_lighting_set_lights(re_lighting *l, const re_lights *L) try {
         float mn[3] = { 3.4e38f, 3.4e38f, 3.4e38f }, mx[3] = { -3.4e38f, -3.4e38f, -3.4e38f };
         for (uint32_t i = 0; i < L->n_spot; i++) {
             for (int k = 0; k < 3; k++) { const float v = L->spot_pos[3 * i + k]; if (v < mn[k]) mn[k] = v; if (v > mx[k]) mx[k] = v; }   // (comparisons with NaN are false: it takes no part)
-            if (L->spot_radius[i] > rmax) rmax = L->spot_radius[i];
+            const float r = L->spot_radius[i];
+            if (!(r <= rmax)) rmax = r == r ? r : __builtin_inff();                                                                            // (a NaN radius lights every pixel in the oracle: unbounded reach)
         }
         float best = -1.0f;
         for (int k = 0; k < 3; k++) { const float e = mx[k] - mn[k]; if (e > best && e < 3.0e38f) { best = e; axis = (uint32_t)k; } }
