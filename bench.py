@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- entities/sec through cull + transform on the BASELINE.json workload.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A step is ONE FRAME of the hot path over the resident world, as a frame loop that draws every frame sees it:
 re_cull_pack (visibility query over the spatial hash + frustum / logic cull + instance pack, with the
@@ -13,10 +13,11 @@ N=1: BASELINE.json configs[1] -- 10,077,696 static entities, one per level-0 wor
 fill), one camera frustum, far = 1000.  `value` = entities / median frame time of the K timed frames (median of
 >= 100 frames, so K >= 100); `ms_per_step` = wall time of exactly K timed frames / K.  --dump-outputs DIR writes what the last
 timed frame returned to its caller as DIR/<name>.npy (inputs are synthetic and fixed: two builds compare output for output).
-The same run also reports, as labelled extras: the
-pipelined throughput of asynchronous frames, far = 8192 (wide frustum, ~500 K instances: the large pack path),
-configs[2] (100,777 rotating bodies: tick + cull) incl. a tick of every dynamic entity, configs[4] (deferred
-lighting), the CPU rows, and a full-size check of the visible set against the CPU oracle.
+A plain run does only that: set up, warm up, time the K steps, dump, print the line.  --full also reports, as labelled extras:
+K1's own launches beyond those of the timed region (>= 96), kernel event times, the pipelined throughput of asynchronous frames,
+the opt-in one-launch frame, far = 8192 (wide frustum, ~500 K instances: the large pack path), configs[2] (100,777 rotating
+bodies: tick + cull) incl. a tick of every dynamic entity, configs[4] (deferred lighting), the CPU rows, and a full-size check
+of the visible set against the CPU oracle.
 N>1 (weak scaling, configs[3] at N=8): N x 10,077,696 entities sharded by contiguous section-key range, one process
 per GPU, an RCCL all-gather of every GPU's packed visible-instance slab each frame; the frame ends when the
 gathered buffer is complete.  Rank 0 prints ONE JSON line.
@@ -52,13 +53,16 @@ def parse():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", choices=["default", "visible", "lighting"], default="default",
-                    help="default: the visible-set headline + every extra leg; visible: headline only; lighting: configs[4] only")
+                    help="default: the visible-set headline (+ every extra leg with --full); visible: headline only; lighting: configs[4] only")
     ap.add_argument("--far", type=float, default=1000.0, help="camera far draw distance (reference default 1000, main.rs:23)")
     ap.add_argument("--axis", type=int, default=PER_GPU_AXIS, help="sections per axis per GPU (216 -> 10,077,696 entities)")
     ap.add_argument("--spinner-every", type=int, default=0, help="0 = configs[1] (all static); 100 = configs[2] (100k rotating bodies)")
     ap.add_argument("--tick-all", action="store_true", help="tick every dynamic entity (RE_TICK_ALL_DYNAMIC) instead of the visible ones")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the far=8192 / configs[2] / lighting legs")
+    ap.add_argument("--full", action="store_true", help="besides the headline, run everything else the benchmark measures or checks: further K1 launches, kernel event "
+                                                        "times, asynchronous and one-launch frames, the CPU rows and the full-size check against the CPU oracle, the "
+                                                        "far=8192 / configs[2] / lighting legs; --config lighting: the oracle's pair count, the flop model and the check of the image")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU rows and the full-size check")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the far=8192 / configs[2] / lighting legs")
     ap.add_argument("--force-large-pack", action="store_true", help="always use the multi-kernel pack")
     ap.add_argument("--cpu-sample-axis", type=int, default=100)
     ap.add_argument("--probe", action="store_true", help="opt-in variant: visibility query by hash probes of the candidate cells (RE_CFG_PROBE) instead of the key stream")
@@ -216,7 +220,7 @@ def main():
             dist.init_process_group(backend)
     if a.config == "lighting":
         if rank == 0:
-            out = lighting_leg(headline=True, steps=a.steps, warmup=a.warmup, dump_dir=a.dump_outputs)
+            out = lighting_leg(headline=True, steps=a.steps, warmup=a.warmup, dump_dir=a.dump_outputs, full=a.full)
             print(json.dumps(out))
         if dist is not None:
             dist.destroy_process_group()
@@ -227,11 +231,13 @@ def main():
     F = R._capi
 
     atomic = 64 if world == 1 else 32            # 432 sections per axis need atomic 32
-    extras = world == 1 and a.config == "default" and not a.no_extras and a.far == 1000.0 and not a.spinner_every and a.axis == PER_GPU_AXIS and not a.probe
+    legs = world == 1 and a.config == "default" and not a.no_extras and a.far == 1000.0 and not a.spinner_every and a.axis == PER_GPU_AXIS and not a.probe
+    extras = legs and a.full
     t0 = time.time()
     ents, dims, first = make_shard(rank, world, a.axis, atomic, a.spinner_every)
     n_local = len(ents)
-    cap = max(1 << 16, n_local // 2) if (a.far > 2000 or extras) else 1 << 16      # the far=8192 leg packs ~500 K instances
+    # the far=8192 leg packs ~500 K instances; the capacity follows `legs`, not `extras`, so that a plain run times its frames on the same allocation as --full
+    cap = max(1 << 16, n_local // 2) if (a.far > 2000 or legs) else 1 << 16
     p = R.Pipeline(16384, atomic, device=local, max_instances=cap, flags=F.CFG_PROBE if a.probe else 0)
     p.register_model_instances(ents)
     stats = p.stats()
@@ -323,9 +329,9 @@ def main():
     med_frames = list(wall)                            # exactly the K timed frames (SURVEY 8d asks for K >= 100)
     if a.dump_outputs:                                 # before any further frame overwrites the outputs of the last timed one
         dump_frame(p, vis, tick, a.dump_outputs, "" if world == 1 else "_rank%d" % rank)
-    # the dominant kernel's own launches: at least K1_MIN_LAUNCHES of them whatever --steps was (the timed region alone holds steps / TIMING_EVERY),
+    # --full: the dominant kernel's own launches: at least K1_MIN_LAUNCHES of them whatever --steps was (the timed region alone holds steps / TIMING_EVERY),
     # every launch of further synchronous frames of the same loop, directly behind the timed region
-    n_more = max(K1_MIN_LAUNCHES - len(k1_region), 0)
+    n_more = max(K1_MIN_LAUNCHES - len(k1_region), 0) if a.full else 0
     k1_more = np.zeros(0, np.float32)
     if n_more:
         p.timing_begin(n_more, every=1)
@@ -381,7 +387,7 @@ def main():
                          "achieved": gbs(bytes_comp, k1_mean), "frac": (gbs(bytes_comp, k1_mean) or 0) / HBM_PEAK_GBS if k1_mean == k1_mean else None,
                          "achieved_survey_8d": gbs(bytes_8d, k1_mean), "frac_survey_8d": (gbs(bytes_8d, k1_mean) or 0) / HBM_PEAK_GBS if k1_mean == k1_mean else None,
                          "basis": ("achieved / frac use bytes_compulsory (what this layout must move) over the mean of launches_timed launches (HIP events on the dispatches: those of the timed region "
-                                   "+ further synchronous frames of the same loop); frac_survey_8d > 1 means the kernel does not move SURVEY 8d's bytes: sections outside the frustum cost only their "
+                                   "+ with --full further synchronous frames of the same loop); frac_survey_8d > 1 means the kernel does not move SURVEY 8d's bytes: sections outside the frustum cost only their "
                                    "%d-byte stream key.  The %d MB key array is re-read every frame and stays resident in the 256 MiB Infinity Cache between frames, so this stream is served by the "
                                    "Infinity Cache, not by HBM: the fraction of the 8 TB/s HBM peak is a label for the byte rate, not a bound the kernel runs against (gfx950's FETCH_SIZE counts "
                                    "Infinity-Cache hits too)" % (key_bytes, key_bytes * slots // 1000000)),
@@ -389,7 +395,7 @@ def main():
                          "traffic": traffic, "traffic_source": tr_src},
             "setup_s": t_setup, "cpu_affinity": affinity,
         }
-        if world == 1:
+        if world == 1 and a.full:
             kt = kernel_times(p, camc, 16, a.tick_all)
             out["kernel_us"] = kt
             per = pipelined_frames(p, camc, 64, a.tick_all); per = pipelined_frames(p, camc, max(a.steps, 200), a.tick_all)
@@ -404,7 +410,7 @@ def main():
             out["one_launch_sync"] = {"frame_ms_median": float(np.median(us1)) * 1e-3, "entities_per_s": n_total / (float(np.median(us1)) * 1e-6),
                                       "scan_launch_us_incl_publication": float(np.mean(k1)) if len(k1) else None,
                                       "note": "RE_CULL_ONE_LAUNCH: k_scan_cull_sync + k_pack_small(move only); opt-in, not the default (DESIGN.md section 4)"}
-        if not a.no_cpu_baseline and world == 1:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             gpu_frame = p.cull_and_pack(camc, copy=True) if not a.spinner_every else None
             out["cpu_baseline"], out["cpu_optimised"], out["full_size_check"] = cpu_baseline(a, atomic, n_total, dims, first, gpu_frame)
         p.close()
@@ -545,10 +551,10 @@ def spinner_leg(R, a, atomic):
     return out
 
 
-def lighting_leg(headline, steps=20, warmup=3, dump_dir=None):
+def lighting_leg(headline, steps=20, warmup=3, dump_dir=None, full=True):
     """configs[4]: deferred lighting of a 4096 x 4096 synthetic G-buffer with 4096 radius ('spot') lights as a HIP compute kernel.
-    dump_dir: the image of the last timed launch as a fixed, seeded sample of DUMP_PIXELS pixels (lit_pixels, RGBA) and their indices"""
-    import oracle as ro
+    dump_dir: the image of the last timed launch as a fixed, seeded sample of DUMP_PIXELS pixels (lit_pixels, RGBA) and their indices.
+    full: also the oracle's count of (pixel, light) pairs, the flop model built on it and the sampled check of the image against the oracle"""
     from render_engine_amd import lighting
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     W = H = 4096; NL = 4096
@@ -565,35 +571,38 @@ def lighting_leg(headline, steps=20, warmup=3, dump_dir=None):
     if dump_dir:
         pix = np.sort(np.random.default_rng(DUMP_SEED).choice(W * H, DUMP_PIXELS, replace=False)).astype(np.uint32)
         _save(dump_dir, {"lit_pixel_index": pix.astype(np.float64), "lit_pixels": dl.read_pixels(pix)})
-    keep = []
-    S = lighting.fill_lights_struct(ro.LightsC(), L, keep)
-    pairs = ro.lighting_spot_pairs(pos, S)             # exact count of (pixel, light within its radius) pairs: the oracle is the counter, not the thing measured
-    # sampled check of the full-size image against the CPU evaluation of the GLSL (tolerance 1e-4, BASELINE.json)
-    idx = (np.arange(2048, dtype=np.uint64) * np.uint64(8191 * 4099 + 7) % np.uint64(W * H)).astype(np.uint32)
-    err = float(np.abs(dl.read_pixels(idx) - ro.deferred_lighting(pos, nrm, alb, S, idx=idx)).max())
-    if err > 1e-4:
-        raise SystemExit("lighting: GPU image differs from the CPU evaluation of the GLSL by %g" % err)
-    dl.close()
     npix = W * H
-    flops = pairs * 150 + 20 * npix                  # ~75 flop per evaluated (pixel, light) term, the spot term is evaluated twice, + 20 per pixel epilogue
     bytes_ = npix * (16 + 16 + 4 + 16)               # gPosition + gNormal RGBA32F, gAlbedoSpec RGBA8 read; FragColor RGBA32F written (gLightPosition is not needed)
-    tf, gb = flops / (t * 1e-6) / 1e12, bytes_ / (t * 1e-6) / 1e9
-    # What binds the kernel is decided by the SQ counters, not by which of the two model ratios below is larger: SQ_INSTS_VALU = 92.8 M wave-instructions per
-    # launch fill 75-85 % of the VALU issue slots of the launch (tools/pmc_sq.sh); valu_frac prices only the 150-flop model of the in-radius
-    # (pixel, light) pairs, about a quarter of what a wave executes (it evaluates a listed light for all 64 lanes when any lane is inside the radius).
-    binds = "fp32 VALU issue (SQ_INSTS_VALU: 75-85 % of the issue slots; hbm_frac and valu_frac are model ratios, not utilisations)"
+    gb = bytes_ / (t * 1e-6) / 1e9
     res = {"workload": "configs[4]: deferred lighting, %dx%d synthetic G-buffer, %d radius-40 'spot' lights (second_pass_frag.glsl:20-139)" % (W, H, NL),
            "kernel": "k_deferred_lighting", "kernel_us": t, "pixels_per_s": npix / (t * 1e-6),
-           "pixel_light_pairs_in_radius": pairs, "pairs_per_pixel": pairs / npix, "flop_model": "150 flop per pair (75 per evaluated term, spot term twice) + 20 per pixel",
-           "gflops": flops / (t * 1e-6) / 1e9, "valu_frac": tf / VALU_PEAK_TFLOPS, "valu_peak_tflops": VALU_PEAK_TFLOPS,
-           "gbs": gb, "hbm_frac": gb / HBM_PEAK_GBS, "hbm_bytes": bytes_, "binding_bound": binds,
-           "max_abs_err_vs_cpu_glsl_2048_pixels": err, "tolerance": 1e-4, "setup_s": t_setup}
+           "gbs": gb, "hbm_frac": gb / HBM_PEAK_GBS, "hbm_bytes": bytes_, "setup_s": t_setup}
+    if full:
+        import oracle as ro
+        keep = []
+        S = lighting.fill_lights_struct(ro.LightsC(), L, keep)
+        pairs = ro.lighting_spot_pairs(pos, S)             # exact count of (pixel, light within its radius) pairs: the oracle is the counter, not the thing measured
+        # sampled check of the full-size image against the CPU evaluation of the GLSL (tolerance 1e-4, BASELINE.json)
+        idx = (np.arange(2048, dtype=np.uint64) * np.uint64(8191 * 4099 + 7) % np.uint64(W * H)).astype(np.uint32)
+        err = float(np.abs(dl.read_pixels(idx) - ro.deferred_lighting(pos, nrm, alb, S, idx=idx)).max())
+        if err > 1e-4:
+            raise SystemExit("lighting: GPU image differs from the CPU evaluation of the GLSL by %g" % err)
+        flops = pairs * 150 + 20 * npix                  # ~75 flop per evaluated (pixel, light) term, the spot term is evaluated twice, + 20 per pixel epilogue
+        tf = flops / (t * 1e-6) / 1e12
+        # What binds the kernel is decided by the SQ counters, not by which of the two model ratios below is larger: SQ_INSTS_VALU = 92.8 M wave-instructions per
+        # launch fill 75-85 % of the VALU issue slots of the launch (tools/pmc_sq.sh); valu_frac prices only the 150-flop model of the in-radius
+        # (pixel, light) pairs, about a quarter of what a wave executes (it evaluates a listed light for all 64 lanes when any lane is inside the radius).
+        binds = "fp32 VALU issue (SQ_INSTS_VALU: 75-85 % of the issue slots; hbm_frac and valu_frac are model ratios, not utilisations)"
+        res.update({"pixel_light_pairs_in_radius": pairs, "pairs_per_pixel": pairs / npix, "flop_model": "150 flop per pair (75 per evaluated term, spot term twice) + 20 per pixel",
+                    "gflops": flops / (t * 1e-6) / 1e9, "valu_frac": tf / VALU_PEAK_TFLOPS, "valu_peak_tflops": VALU_PEAK_TFLOPS, "binding_bound": binds,
+                    "max_abs_err_vs_cpu_glsl_2048_pixels": err, "tolerance": 1e-4})
+    dl.close()
     if not headline:
         return res
     return {"metric": "deferred-lighting pixels/sec (configs[4])", "value": res["pixels_per_s"], "unit": "pixels/s", "n_gpus": 1, "steps": steps, "warmup": warmup,
             "ms_per_step": t * 1e-3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": res["workload"]},
-            "roofline": {"bound": "hbm", "note": "the kernel is fp32-VALU-issue bound (no MFMA: per-light branchy shading), so this HBM fraction is low by construction; the VALU figures are in `lighting`",
+            "roofline": {"bound": "hbm", "note": "the kernel is fp32-VALU-issue bound (no MFMA: per-light branchy shading), so this HBM fraction is low by construction; the VALU figures (--full) are in `lighting`",
                          "achieved": gb, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gb / HBM_PEAK_GBS,
                          "traffic": committed_traffic("lighting")[0], "traffic_source": committed_traffic("lighting")[1]},
             "lighting": res}

@@ -3,6 +3,7 @@
 # (default bench args: the headline leg alone, so that a kernel name means one workload)
 tag=$1; shift
 args=${@:---config visible --no-extras}
+args="--full $args"      # everything the bench runs, not only the timed steps of a plain run: as the committed profiles were taken
 root=${GRAFT_REPO_ROOT:-$PWD}
 cd /tmp && export TMPDIR=/tmp
 for ctr in FETCH_SIZE WRITE_SIZE; do

@@ -2,6 +2,7 @@
 # usage (on the GPU box): tools/pmc_sq.sh <tag> [bench args...] ; wave / instruction counters of the frame kernels (per-dispatch means), one --pmc pass per group
 tag=$1; shift
 args=${@:---spinner-every 100 --tick-all --no-extras}
+args="--full $args"      # everything the bench runs, not only the timed steps of a plain run: as the committed profiles were taken
 root=${GRAFT_REPO_ROOT:-$PWD}
 cd /tmp && export TMPDIR=/tmp
 i=0

@@ -2,6 +2,7 @@
 # usage (on the GPU box): tools/prof_bench.sh <outdir-under-gpurun_out> [bench args...]
 # kernel trace + stats of bench.py; prints the per-kernel averages
 out=$1; shift
+set -- --full "$@"      # everything the bench runs, not only the timed steps of a plain run: as the committed profiles were taken
 root=${GRAFT_REPO_ROOT:-$PWD}
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_$out; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$out -- python $root/bench.py "$@" > $root/gpurun_out/$out.log 2>&1

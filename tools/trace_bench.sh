@@ -1,6 +1,7 @@
 #!/bin/bash
 # kernel timeline of the last frames of bench.py (durations and gaps)
 cd /tmp && export TMPDIR=/tmp
+set -- --full "$@"      # everything the bench runs, not only the timed steps of a plain run: as the committed profiles were taken
 rm -rf $GRAFT_REPO_ROOT/gpurun_out/trace_bench
 rocprofv3 --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/trace_bench -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline "$@" > $GRAFT_REPO_ROOT/gpurun_out/trace_bench.log 2>&1
 python3 - <<PY
