@@ -342,6 +342,36 @@ int re_add_entities(re_ctx *ctx, const re_entities *ents, uint32_t *n_rejected);
 typedef struct { uint32_t this_entity, other_entity; } re_collision;
 int re_collide(re_ctx *ctx, uint32_t flags /*0*/, re_collision *pairs, uint32_t capacity, uint32_t *n_total);
 
+/* ---- entity logic: LogicFlow::update_logic (flows/logic_flow.rs:245, body :662-734, find_always_execute_entities :801-837) up to the callbacks ----
+ * The entity type is an ECS component (ECS::write_entity_type / remove_entity_type / get_entity_type, objects/ecs.rs:481-492, 594-608, 666-670): a
+ * TypeIdentifier per entity, ECS bit 0.  type_identifiers == NULL removes the type of every listed entity.  A batch is checked whole before anything is
+ * written: an unknown or removed id refuses it (RE_E_ARG) and nothing changes.  A type dies with its entity (delete, leaving the world), a reused id
+ * starts without one, re_upload_entities clears them all; entities created by re_add_entities / RE_CHANGE_ADD_ENTITY get theirs through a following
+ * re_set_entity_types.  re_get_entity_type: RE_E_ARG == None (no type, or no such entity). */
+int re_set_entity_types(re_ctx *ctx, const uint32_t *entity_ids, uint32_t n, const uint64_t *type_identifiers /* NULL: remove_entity_type */);
+int re_get_entity_type(re_ctx *ctx, uint32_t entity_id, uint64_t *type_identifier);
+/* InstanceLogic::entity_logic / random_entity_logic (exports/load_models.rs:75-76): which entity types carry which of the two functions.  The call
+ * REPLACES the table (n <= 65535; n == 0 empties it); a duplicate identifier, which == 0 or bits beyond RE_LOGIC_ENTITY | RE_LOGIC_RANDOM refuse it
+ * (RE_E_ARG, the previous table stays).  The table belongs to the logic flow, not to the ECS: it survives re_upload_entities. */
+#define RE_LOGIC_ENTITY 1u
+#define RE_LOGIC_RANDOM 2u
+typedef struct { uint64_t type_identifier; uint32_t which; uint32_t reserved; } re_entity_logic;      /* 16 bytes */
+int re_set_entity_logic(re_ctx *ctx, const re_entity_logic *table, uint32_t n);
+/* The call list of the frame: one record per entity that update_logic hands to apply_entity_logic at least once and whose type is in the table --
+ * logic_index = index of the type in the table of re_set_entity_logic, which = the functions registered for it, times = how often the reference
+ * calls them this frame (1, or 2 for an entity of a world section listed twice in visible_sections_vec: logic box and frustum).
+ *   local (non-static) entities of the active visible world sections, once per listing of the section;
+ *   entities of the shared sections those link, once, when the shared AABB is in view of the logic or the render culler;
+ *   entities with RE_F_ALWAYS_EXEC none of whose world sections is in visible_sections_map.
+ * Dead entities, RE_F_PHANTOM replicas and entities outside the tree are never listed; RE_CULL_EMIT_DUPLICATES has no influence.
+ * Call order of a frame as in LogicFlow::execute_logic (:230-255): re_cull_pack, re_collide, re_logic_list, re_tick.  The list is this frame's only
+ * BETWEEN the cull and the tick: it is built from the visibility query of the last re_cull_pack (an asynchronous one is finished first) on the tree
+ * as it stands, before the tick moves anything.  RE_E_STATE without a world or before the first cull.
+ * The records come in no particular order (the reference's order depends on thread timing).  *n_total = number of records; the first `capacity`
+ * are written to `calls` (host memory).  capacity without a buffer, or flags != 0: RE_E_ARG. */
+typedef struct { uint32_t entity_id; uint16_t logic_index; uint8_t which, times; } re_logic_call;   /* 8 bytes */
+int re_logic_list(re_ctx *ctx, uint32_t flags /*0*/, re_logic_call *calls, uint32_t capacity, uint32_t *n_total);
+
 /* ECS read-back for user logic (LogicFunction reads components through &ECS, exports/logic_components.rs:15-18).  A component the entity does not
  * carry (never written, or removed by RE_CHANGE_REMOVE_COMPONENT) yields RE_E_ARG == ECS::get_copy -> None (objects/ecs.rs:653-664). */
 int re_read_component(re_ctx *ctx, uint32_t entity_id, int component, void *dst);
@@ -350,7 +380,7 @@ int re_read_component(re_ctx *ctx, uint32_t entity_id, int component, void *dst)
  * The reference keeps one bitset per entity: bit i is set once the i-th REGISTERED component type has been written for the entity and cleared by
  * remove_component / remove_entity.  Bit positions are registration order: ECS::new registers TypeIdentifier first (ecs.rs:141), LogicFlow::new the
  * engine's components after it (flows/logic_flow.rs:83-110).  re_ecs_bitset returns that bitset (bitsets[entity][0..4] as one little-endian word). */
-#define RE_ECS_BIT_TYPE_IDENTIFIER      0   /* the entity-type marker (write_entity_type); not tracked here: always 0 */
+#define RE_ECS_BIT_TYPE_IDENTIFIER      0   /* the entity-type marker: set while the entity carries a type (re_set_entity_types; write_entity_type is a write_component::<TypeIdentifier>) */
 #define RE_ECS_BIT_CAN_CAUSE_COLLISIONS 2
 #define RE_ECS_BIT_HAS_MOVED            3
 #define RE_ECS_BIT_POSITION             4

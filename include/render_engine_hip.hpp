@@ -192,6 +192,7 @@ struct FrameResult {
     std::vector<re_instance_range> groups;                  // (LOD-adjusted ModelId, render system, sortable) -> InstanceRange
     std::vector<EntityId> entity_ids; std::vector<float> matrices;   // host copies (filled when execute(.., copy = true))
     std::vector<re_collision> collisions;                            // (this_entity, other_entity) of every collision-logic invocation (execute(.., collide = true))
+    std::vector<re_logic_call> logic_calls;                          // the entity-logic calls of the frame (execute(.., logic = true)): entity, index into the registered logic table, functions, times
     re_tick_result tick{};
 };
 
@@ -261,10 +262,32 @@ class Pipeline {
     void write_always_execute_logic(EntityId e) { row(e).flags |= RE_F_ALWAYS_EXEC; uploaded_ = false; }
     void write_out_of_bounds_logic(EntityId e) { row(e).flags |= RE_F_OOB_LOGIC; uploaded_ = false; }                           // the entity type has OutOfBoundsLogic
 
+    // ECS::write_entity_type / remove_entity_type (objects/ecs.rs:481-492, 594-608).  The type of an entity that has not reached
+    // the GPU yet travels with its registration (upload_if_needed); re_upload_entities clears the types of a world, so a replaced world gets them again.
+    void write_entity_type(EntityId e, uint64_t type_identifier) {
+        Row &r = row(e); r.type = type_identifier; r.typed = true;
+        if (in_world(e)) check(re_set_entity_types(ctx_, &e, 1u, &type_identifier), "re_set_entity_types");
+    }
+    void remove_entity_type(EntityId e) {
+        row(e).typed = false;
+        if (in_world(e)) check(re_set_entity_types(ctx_, &e, 1u, nullptr), "re_set_entity_types");
+    }
+    // InstanceLogic::entity_logic / random_entity_logic (exports/load_models.rs:75-76): the type carries the functions `which` (RE_LOGIC_ENTITY | RE_LOGIC_RANDOM).
+    // Returns the index FrameResult::logic_calls names the type by.
+    uint16_t register_entity_logic(uint64_t type_identifier, uint32_t which) {
+        size_t i = 0;
+        while (i < logic_table_.size() && logic_table_[i].type_identifier != type_identifier) i++;
+        if (i == logic_table_.size()) logic_table_.push_back(re_entity_logic{ type_identifier, 0u, 0u });
+        logic_table_[i].which |= which;
+        check(re_set_entity_logic(ctx_, logic_table_.data(), (uint32_t)logic_table_.size()), "re_set_entity_logic");
+        return (uint16_t)i;
+    }
     // Pipeline::execute (flows/pipeline.rs:212-276) for this path: both visibility queries + render gather, then the kinematic tick
     // collide: also run the collision phase of LogicFlow::execute (logic_flow.rs:243) between the visibility queries and the tick; the
     // caller dispatches FrameResult::collisions to the CollisionFunction of each this_entity's type
-    FrameResult execute(const Camera &camera, float delta_time, bool copy = false, bool emit_duplicates = false, bool collide = false) {
+    // logic: also build the call list of LogicFlow::update_logic (logic_flow.rs:245) before the tick; the caller runs the registered functions of
+    // FrameResult::logic_calls and hands the change requests they return to apply_change
+    FrameResult execute(const Camera &camera, float delta_time, bool copy = false, bool emit_duplicates = false, bool collide = false, bool logic = false) {
         upload_if_needed();
         executed_ = true;
         re_camera cam{};
@@ -287,6 +310,11 @@ class Pipeline {
             uint32_t n = 0; check(re_collide(ctx_, 0u, nullptr, 0u, &n), "re_collide");
             out.collisions.resize(n);
             if (n) check(re_collide(ctx_, 0u, out.collisions.data(), n, &n), "re_collide");
+        }
+        if (logic) {
+            uint32_t n = 0; check(re_logic_list(ctx_, 0u, nullptr, 0u, &n), "re_logic_list");
+            out.logic_calls.resize(n);
+            if (n) check(re_logic_list(ctx_, 0u, out.logic_calls.data(), n, &n), "re_logic_list");
         }
         check(re_tick(ctx_, delta_time, 0u, &out.tick), "re_tick");
         return out;
@@ -366,7 +394,9 @@ class Pipeline {
     struct Row {
         EntityId id = 0; ModelId model; uint32_t sortable = 0, flags = 0; StaticAABB original{};
         TVec3 pos{}, scale{ 1, 1, 1 }, vel{}, acc{}; Rotation rot{}; VelocityRotation rotvel{}; AccelerationRotation rotacc{}; bool placed = false;
+        uint64_t type = 0; bool typed = false;                                          // TypeIdentifier (write_entity_type)
     };
+    bool in_world(EntityId e) const { return e < n_sent_ && (uploaded_ || executed_) && rows_[e].placed; }   // the GPU world holds the entity and will not be replaced
     Row &row(EntityId e) { if (e >= rows_.size()) throw Error(RE_E_ARG, "unknown entity"); return rows_[e]; }
     void check(int rc, const char *what) { if (rc != RE_OK) throw Error(rc, std::string(what) + ": " + re_last_error(ctx_)); }
     void read(EntityId e, int component, void *dst) { upload_if_needed(); check(re_read_component(ctx_, e, component, dst), "re_read_component"); }
@@ -396,9 +426,13 @@ class Pipeline {
         E.rotation_velocity = rv.data(); E.rotation_acceleration = ra.data();
         if (executed_) { uint32_t rej = 0; check(re_add_entities(ctx_, &E, &rej), "re_add_entities"); n_rejected_ += rej; }
         else check(re_upload_entities(ctx_, &E, &n_rejected_), "re_upload_entities");
+        std::vector<uint32_t> typed_id; std::vector<uint64_t> typed;                   // the types of the entities that upload carried
+        for (size_t ri = first; ri < rows_.size(); ri++) if (rows_[ri].placed && rows_[ri].typed) { typed_id.push_back(rows_[ri].id); typed.push_back(rows_[ri].type); }
+        if (!typed_id.empty()) check(re_set_entity_types(ctx_, typed_id.data(), (uint32_t)typed_id.size(), typed.data()), "re_set_entity_types");
         n_sent_ = rows_.size(); uploaded_ = true;
     }
     re_ctx *ctx_ = nullptr; std::vector<Row> rows_; bool uploaded_ = false, executed_ = false; uint32_t n_rejected_ = 0; size_t n_sent_ = 0;
+    std::vector<re_entity_logic> logic_table_;
 };
 
 inline void EntityTransformationBuilder::apply_choices(StaticAABB original_aabb, Pipeline &pipeline) {     // entity_transformer.rs:55-75, 99-142

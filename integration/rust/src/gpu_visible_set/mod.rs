@@ -10,7 +10,7 @@ use std::ffi::CStr;
 use std::mem::MaybeUninit;
 
 /// One resident copy of the world on one GPU.
-pub struct GpuVisibleSet { ctx: *mut ReCtx, collision_pairs: Vec<ReCollision> }
+pub struct GpuVisibleSet { ctx: *mut ReCtx, collision_pairs: Vec<ReCollision>, logic_list: Vec<ReLogicCall> }
 
 // the context is driven from the render thread only (Pipeline::execute), like the flows it replaces
 unsafe impl Send for GpuVisibleSet {}
@@ -51,7 +51,7 @@ impl GpuVisibleSet {
         let mut ctx: *mut ReCtx = std::ptr::null_mut();
         let rc = unsafe { re_create(&cfg, &mut ctx) };
         if rc != RE_OK { return Err(GpuError { code: rc, message: last_error(std::ptr::null()) }); }
-        Ok(GpuVisibleSet { ctx, collision_pairs: Vec::with_capacity(4096) })
+        Ok(GpuVisibleSet { ctx, collision_pairs: Vec::with_capacity(4096), logic_list: Vec::with_capacity(4096) })
     }
 
     fn check(&self, rc: i32) -> Result<(), GpuError> {
@@ -266,6 +266,39 @@ impl GpuVisibleSet {
             self.check(rc)?;
             if n <= cap { unsafe { self.collision_pairs.set_len(n as usize) }; return Ok(&self.collision_pairs); }
             self.collision_pairs = Vec::with_capacity(n as usize + n as usize / 4);      // grew past the buffer: once more with room
+        }
+    }
+
+    /// ECS::write_entity_type (objects/ecs.rs:481-492) for a batch of entities; `types: None` is remove_entity_type.  Entities added later
+    /// (add_entities, RE_CHANGE_ADD_ENTITY) get their type through a following call; an upload clears all types.
+    pub fn set_entity_types(&mut self, ids: &[u32], types: Option<&[u64]>) -> Result<(), GpuError> {
+        if let Some(t) = types { assert_eq!(t.len(), ids.len()); }
+        let p = types.map_or(std::ptr::null(), |t| t.as_ptr());
+        self.check(unsafe { ffi::re_set_entity_types(self.ctx, ids.as_ptr(), ids.len() as u32, p) })
+    }
+
+    /// ECS::get_entity_type (objects/ecs.rs:666-670)
+    pub fn get_entity_type(&mut self, id: u32) -> Option<u64> {
+        let mut t = 0u64;
+        if unsafe { ffi::re_get_entity_type(self.ctx, id, &mut t) } == RE_OK { Some(t) } else { None }
+    }
+
+    /// InstanceLogic::entity_logic / random_entity_logic (exports/load_models.rs:75-76): the types that carry a function, in the order
+    /// `ReLogicCall::logic_index` refers to.  Replaces the table; it survives uploads.
+    pub fn set_entity_logic(&mut self, table: &[ReEntityLogic]) -> Result<(), GpuError> {
+        self.check(unsafe { ffi::re_set_entity_logic(self.ctx, table.as_ptr(), table.len() as u32) })
+    }
+
+    /// flows/logic_flow.rs:245: `update_logic` up to the callbacks, after `collide` and before `tick`: one record per entity whose type is in
+    /// the table and that the reference hands to apply_entity_logic this frame (`times` = how often), in no particular order.
+    pub fn logic_calls(&mut self) -> Result<&[ReLogicCall], GpuError> {
+        loop {
+            let mut n = 0u32;
+            let cap = self.logic_list.capacity() as u32;
+            let rc = unsafe { ffi::re_logic_list(self.ctx, 0, self.logic_list.as_mut_ptr(), cap, &mut n) };
+            self.check(rc)?;
+            if n <= cap { unsafe { self.logic_list.set_len(n as usize) }; return Ok(&self.logic_list); }
+            self.logic_list = Vec::with_capacity(n as usize + n as usize / 4);          // grew past the buffer: once more with room
         }
     }
 

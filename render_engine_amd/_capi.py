@@ -3,6 +3,8 @@ missing or cannot be loaded the import of the product path fails loudly."""
 import ctypes as C
 import os
 
+import numpy as np
+
 from . import build as _build
 
 RE_OK = 0
@@ -142,9 +144,25 @@ class ShadowStats(C.Structure):
     _fields_ = [("n_steps", C.c_uint32), ("n_host_waits", C.c_uint32), ("n_column_uploads", C.c_uint32)]
 
 
+# the entity-logic call list (re_logic_list): re_entity_logic (16 bytes) and re_logic_call (8 bytes)
+LOGIC_ENTITY, LOGIC_RANDOM = 1, 2
+
+
+class EntityLogic(C.Structure):
+    _fields_ = [("type_identifier", C.c_uint64), ("which", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class LogicCall(C.Structure):
+    _fields_ = [("entity_id", C.c_uint32), ("logic_index", C.c_uint16), ("which", C.c_uint8), ("times", C.c_uint8)]
+
+
+LOGIC_CALL_DT = np.dtype([("entity_id", "u4"), ("logic_index", "u2"), ("which", "u1"), ("times", "u1")])     # re_logic_call as a numpy record
+
+
 # every symbol include/re_hip.h declares
 EXPORTS = ["re_create", "re_destroy", "re_last_error", "re_abi_version", "re_upload_entities", "re_set_model_lod", "re_cull_pack", "re_tick",
-           "re_apply_changes", "re_apply_changes_ex", "re_add_entities", "re_set_shard_range", "re_list_migrants", "re_export_entities", "re_collide", "re_wait", "re_run_frames", "re_comm_unique_id", "re_comm_init", "re_comm_adopt", "re_comm_destroy", "re_allgather_visible", "re_gather_wait", "re_copy_visible", "re_set_output_buffers", "re_set_output_count", "re_read_component", "re_set_light_information", "re_ecs_bitset", "re_ecs_query", "re_visible_lights", "re_section_keys", "re_get_out_of_bounds", "re_get_stats",
+           "re_apply_changes", "re_apply_changes_ex", "re_add_entities", "re_set_shard_range", "re_list_migrants", "re_export_entities", "re_collide",
+           "re_set_entity_types", "re_get_entity_type", "re_set_entity_logic", "re_logic_list", "re_wait", "re_run_frames", "re_comm_unique_id", "re_comm_init", "re_comm_adopt", "re_comm_destroy", "re_allgather_visible", "re_gather_wait", "re_copy_visible", "re_set_output_buffers", "re_set_output_count", "re_read_component", "re_set_light_information", "re_ecs_bitset", "re_ecs_query", "re_visible_lights", "re_section_keys", "re_get_out_of_bounds", "re_get_stats",
            "re_debug_get_sections", "re_debug_get_shared_sections", "re_debug_get_visible_sections", "re_debug_copy_to_host", "re_get_timings", "re_get_stream",
            "re_timing_begin", "re_timing_collect", "re_get_last_candidates", "re_debug_get_plan_stats",
            "re_lighting_create", "re_lighting_destroy", "re_lighting_last_error", "re_lighting_upload_gbuffer", "re_lighting_set_lights",
@@ -159,7 +177,6 @@ _lib = None
 def device_to_host(handle, ptr, nbytes):
     """bytes of device memory through the library itself (re_debug_copy_to_host): the process may hold a second HIP runtime (a PyTorch wheel brings its
     own), and a pointer of this library means nothing to that one"""
-    import numpy as np
     out = np.zeros(max(nbytes, 1), np.uint8)
     rc = load().re_debug_copy_to_host(handle, ptr, out.ctypes.data, nbytes)
     if rc != 0:
@@ -199,6 +216,10 @@ def load():
     L.re_allgather_visible.restype = C.c_int; L.re_allgather_visible.argtypes = [vp, C.c_uint32, C.POINTER(Gathered)]
     L.re_gather_wait.restype = C.c_int; L.re_gather_wait.argtypes = [vp, C.POINTER(Gathered)]
     L.re_collide.restype = C.c_int; L.re_collide.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.re_set_entity_types.restype = C.c_int; L.re_set_entity_types.argtypes = [vp, vp, C.c_uint32, vp]
+    L.re_get_entity_type.restype = C.c_int; L.re_get_entity_type.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.re_set_entity_logic.restype = C.c_int; L.re_set_entity_logic.argtypes = [vp, vp, C.c_uint32]
+    L.re_logic_list.restype = C.c_int; L.re_logic_list.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     L.re_apply_changes.restype = C.c_int; L.re_apply_changes.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(TickResult)]
     L.re_apply_changes_ex.restype = C.c_int; L.re_apply_changes_ex.argtypes = [vp, vp, C.c_uint32, C.POINTER(Entities), C.c_uint32, C.POINTER(TickResult)]
     L.re_add_entities.restype = C.c_int; L.re_add_entities.argtypes = [vp, C.POINTER(Entities), _u32p]

@@ -248,6 +248,13 @@ struct re_ctx {
         char buf[512]; va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
         err = buf; return code;
     }
+    // entity logic (re_logic_list).  Entity types by row: the host copy is the truth (nothing on the device writes them).  The logic table belongs to the flow and
+    // survives uploads.  On the device: the rows whose type is in the table, ascending, and next to each its word (table index | which << 16); rebuilt only when a
+    // setter or an upload has marked them dirty -- moves, make-static, wake-up and deletes need no rebuild (the kernel reads the live flags, row_cell and stamps).
+    std::vector<uint64_t> h_type; std::vector<uint8_t> h_typed;                // [row]; rows beyond the vectors carry no type
+    std::vector<re_entity_logic> logic_table; std::unordered_map<uint64_t, uint32_t> logic_index;   // TypeIdentifier -> table index
+    DevBuf<uint32_t> d_logic_rows, d_logic_words; DevBuf<unsigned long long> d_logic_out; DevBuf<LogicHeader> d_logic_hdr; uint32_t logic_n = 0, logic_calls = 0; bool logic_dirty = true;
+    LogicPublished *h_logic = nullptr, *d_hlogic = nullptr;                    // mapped host block the kernel publishes the count into
 };
 
 #define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return (ctx)->fail(RE_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
@@ -335,6 +342,7 @@ static void free_world(re_ctx *c) {
     uint64_t *a = &c->dev_bytes;
     c->d_light_rows.release(nullptr); c->d_light_out.release(nullptr); c->light_rows_dirty = true;
     c->h_li.clear(); c->h_li_col.clear(); c->d_li.release(nullptr); c->li_dirty = true;
+    c->h_type.clear(); c->h_typed.clear(); c->d_logic_rows.release(nullptr); c->d_logic_words.release(nullptr); c->d_logic_out.release(nullptr); c->logic_n = 0; c->logic_dirty = true;   // (the logic table stays)
     c->d_cell_cap.release(a); c->d_cell_links.release(a); c->h_linked_slots.clear(); c->d_base_keys.release(a); c->d_ovl_keys.release(nullptr); c->d_ovl_slots.release(nullptr); c->rb_base_dirty = c->rb_ovl_dirty = true; c->stale_slots.clear();
     c->d_hrb_list.release(nullptr); c->d_hrb_nk.release(nullptr); c->d_hrb_keys.release(nullptr); c->d_chg_ops.release(nullptr); c->d_chg_list.release(nullptr);
     if (c->h_chg) { (void)hipHostFree(c->h_chg); c->h_chg = nullptr; c->d_chg = nullptr; }
@@ -367,6 +375,8 @@ extern "C" void re_destroy(re_ctx *c) try {
     if (c->comm.comm) comm_release(c);
     free_world(c);
     if (c->h_col) { (void)hipHostFree(c->h_col); c->h_col = nullptr; }        // lives with the collision scratch lists (kept across uploads)
+    if (c->h_logic) { (void)hipHostFree(c->h_logic); c->h_logic = nullptr; }
+    c->d_logic_hdr.release(nullptr);
     for (auto &ev : c->ev) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->k1_events) (void)hipEventDestroy(ev);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -3632,6 +3642,7 @@ extern "C" int re_ecs_bitset(re_ctx *c, uint32_t entity_id, uint32_t *bits) try 
     HIPCHK(c, hipMemcpy(&fl, c->d_flags.p + r, 4, hipMemcpyDeviceToHost));     // the device column is the truth (HasMoved / HasRotated are maintained by the tick)
     *bits = ecs_bits_of_flags(fl);
     if (!(fl & F_DEAD) && c->h_li.count(r)) *bits |= 1u << RE_ECS_BIT_LIGHT_INFORMATION;
+    if (!(fl & F_DEAD) && r < c->h_typed.size() && c->h_typed[r]) *bits |= 1u << RE_ECS_BIT_TYPE_IDENTIFIER;
     return RE_OK;
 } RE_ABI_GUARD(c, "re_ecs_bitset")
 // The world sections an entity is registered in -- one key (its unique section) or the 2..8 keys its shared section links --, for a loader that spreads
@@ -4000,3 +4011,128 @@ extern "C" int re_get_last_candidates(re_ctx *c, uint32_t *n_candidates) try {
     if (!c || !c->h_res || !n_candidates) return RE_E_ARG;
     *n_candidates = c->h_res->n_candidates; return RE_OK;
 } RE_ABI_GUARD(c, "re_get_last_candidates")
+
+// ------------------------------------------------------------------------------------------------
+// Entity logic: LogicFlow::update_logic (flows/logic_flow.rs:245, :662-734, :801-837) up to the callbacks.  The entity types (ECS::write_entity_type)
+// live on the host by row, the logic table (InstanceLogic::entity_logic / random_entity_logic) with the flow; the device holds the rows whose type is in
+// the table, and k_logic_list (re_logic.hip) turns them into the frame's call list with the gate of the tick.
+// ------------------------------------------------------------------------------------------------
+extern "C" int re_set_entity_types(re_ctx *c, const uint32_t *entity_ids, uint32_t n, const uint64_t *type_identifiers) try {
+    if (!c) return RE_E_ARG;
+    if (n && !entity_ids) return c->fail(RE_E_ARG, "re_set_entity_types: entity_ids is NULL");
+    if (!c->h_res) return c->fail(RE_E_STATE, "re_set_entity_types: no world uploaded");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc_ = resolve(c); if (rc_ != RE_OK) return rc_; }                     // (removals of the last tick are in h_flags)
+    std::vector<uint32_t> rows(n);
+    for (uint32_t i = 0; i < n; i++) {                                          // the whole batch is checked before anything is written
+        if (!c->row_of(entity_ids[i], &rows[i])) return c->fail(RE_E_ARG, "re_set_entity_types: unknown entity %u", entity_ids[i]);
+        if (c->h_flags[rows[i]] & F_DEAD) return c->fail(RE_E_ARG, "re_set_entity_types: entity %u was removed", entity_ids[i]);
+    }
+    if (n && c->h_typed.size() < c->n) { c->h_type.resize(c->n, 0ull); c->h_typed.resize(c->n, 0); }
+    for (uint32_t i = 0; i < n; i++) {
+        if (type_identifiers) { c->h_type[rows[i]] = type_identifiers[i]; c->h_typed[rows[i]] = 1; }
+        else c->h_typed[rows[i]] = 0;
+    }
+    if (n) c->logic_dirty = true;
+    return RE_OK;
+} RE_ABI_GUARD(c, "re_set_entity_types")
+
+extern "C" int re_get_entity_type(re_ctx *c, uint32_t entity_id, uint64_t *type_identifier) try {
+    if (!c || !type_identifier) return RE_E_ARG;
+    if (!c->h_res) return c->fail(RE_E_STATE, "re_get_entity_type: no world uploaded");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc_ = resolve(c); if (rc_ != RE_OK) return rc_; }
+    uint32_t r = 0;
+    if (!c->row_of(entity_id, &r)) return c->fail(RE_E_ARG, "re_get_entity_type: unknown entity %u", entity_id);
+    if ((c->h_flags[r] & F_DEAD) || r >= c->h_typed.size() || !c->h_typed[r]) return c->fail(RE_E_ARG, "re_get_entity_type: entity %u has no type", entity_id);   // get_copy -> None
+    *type_identifier = c->h_type[r];
+    return RE_OK;
+} RE_ABI_GUARD(c, "re_get_entity_type")
+
+extern "C" int re_set_entity_logic(re_ctx *c, const re_entity_logic *table, uint32_t n) try {
+    if (!c) return RE_E_ARG;
+    if (n && !table) return c->fail(RE_E_ARG, "re_set_entity_logic: table is NULL");
+    if (n > 65535u) return c->fail(RE_E_ARG, "re_set_entity_logic: %u entries (at most 65535)", n);
+    std::unordered_map<uint64_t, uint32_t> index;
+    for (uint32_t i = 0; i < n; i++) {                                          // checked whole before the table is replaced
+        if (!table[i].which || (table[i].which & ~(RE_LOGIC_ENTITY | RE_LOGIC_RANDOM))) return c->fail(RE_E_ARG, "re_set_entity_logic: entry %u: which = 0x%x", i, table[i].which);
+        if (!index.emplace(table[i].type_identifier, i).second) return c->fail(RE_E_ARG, "re_set_entity_logic: entry %u repeats type 0x%llx", i, (unsigned long long)table[i].type_identifier);
+    }
+    c->logic_table.assign(table, table + n); c->logic_index.swap(index); c->logic_dirty = true;
+    return RE_OK;
+} RE_ABI_GUARD(c, "re_set_entity_logic")
+
+// the listed rows on the device: live rows whose type is in the table, ascending row
+static int sync_logic_rows(re_ctx *c) {
+    if (!c->logic_dirty) return RE_OK;
+    std::vector<uint32_t> rows, words;
+    if (!c->logic_index.empty()) {
+        uint64_t last_type = 0; uint32_t last_word = 0; bool have_last = false, last_in = false;      // (worlds type long runs of rows alike)
+        const uint32_t nr = (uint32_t)std::min<size_t>(c->h_typed.size(), c->n);
+        for (uint32_t r = 0; r < nr; r++) {
+            if (!c->h_typed[r] || (c->h_flags[r] & F_DEAD)) continue;
+            const uint64_t t = c->h_type[r];
+            if (!have_last || t != last_type) {
+                auto e = c->logic_index.find(t);
+                have_last = true; last_type = t; last_in = e != c->logic_index.end();
+                if (last_in) last_word = e->second | (c->logic_table[e->second].which << 16);
+            }
+            if (last_in) { rows.push_back(r); words.push_back(last_word); }
+        }
+    }
+    const uint32_t nl = (uint32_t)rows.size();
+    if (nl > c->d_logic_out.n || !c->d_logic_rows.p) {
+        HIPCHK(c, c->d_logic_rows.alloc(nl, nullptr)); HIPCHK(c, c->d_logic_words.alloc(nl, nullptr)); HIPCHK(c, c->d_logic_out.alloc(nl, nullptr));
+    }
+    if (nl) { HIPCHK(c, hipMemcpy(c->d_logic_rows.p, rows.data(), (size_t)nl * 4, hipMemcpyHostToDevice)); HIPCHK(c, hipMemcpy(c->d_logic_words.p, words.data(), (size_t)nl * 4, hipMemcpyHostToDevice)); }
+    c->logic_n = nl; c->logic_dirty = false;
+    return RE_OK;
+}
+
+static_assert(sizeof(re_logic_call) == 8 && sizeof(re_entity_logic) == 16, "record layouts of include/re_hip.h");
+extern "C" int re_logic_list(re_ctx *c, uint32_t flags, re_logic_call *calls, uint32_t capacity, uint32_t *n_total) try {
+    if (!c) return RE_E_ARG;
+    if (flags) return c->fail(RE_E_ARG, "re_logic_list: flags must be 0");
+    if (capacity && !calls) return c->fail(RE_E_ARG, "re_logic_list: capacity without a buffer");
+    if (!c->h_res) return c->fail(RE_E_STATE, "re_logic_list: no world uploaded");
+    if (!c->have_cull) return c->fail(RE_E_STATE, "re_logic_list: the call list follows the visibility query of the frame; call re_cull_pack first");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = c->cull_inflight ? finish_cull(c, nullptr) : resolve(c); if (rc != RE_OK) return rc; }
+    if (c->tick_inflight) { int rc = finish_tick(c, nullptr); if (rc != RE_OK) return rc; }
+    { int rc = sync_logic_rows(c); if (rc != RE_OK) return rc; }
+    if (n_total) *n_total = 0;
+    if (!c->logic_n) return RE_OK;
+    hipStream_t st = c->stream;
+    if (!c->d_logic_hdr.p) {
+        HIPCHK(c, c->d_logic_hdr.alloc(1, nullptr)); HIPCHK(c, hipMemsetAsync(c->d_logic_hdr.p, 0, sizeof(LogicHeader), st));      // cleared once; every call leaves it clean again
+        HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_logic), sizeof(LogicPublished), hipHostMallocMapped | hipHostMallocCoherent)); memset(c->h_logic, 0, sizeof(LogicPublished));
+        HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&c->d_hlogic), c->h_logic, 0));
+    }
+    const uint32_t seq = ++c->logic_calls;
+    hipLaunchKernelGGL(k_logic_list, dim3((c->logic_n + 255u) / 256u), dim3(256), 0, st, c->logic_n, (const uint32_t *)c->d_logic_rows.p, (const uint32_t *)c->d_logic_words.p,
+                       (const uint32_t *)c->d_flags.p, (const uint32_t *)c->d_id.p, (const uint32_t *)c->d_row_cell.p, (const uint32_t *)c->d_cell_stamp.p, (const uint8_t *)c->d_cell_flags.p,
+                       (const int32_t *)c->d_sh_cells.p, (const Aabb *)c->d_sh_aabb.p, (const FrameParams *)c->d_params.p, c->d_logic_hdr.p, c->d_logic_out.p, c->d_hlogic, seq);
+    HIPCHK(c, hipGetLastError());
+    uint32_t nrec = 0;
+    {   // completion: poll the sequence number the last workgroup publishes in mapped host memory (as re_collide does)
+        const volatile uint32_t *flag = &c->h_logic->seq;
+        const auto t0 = std::chrono::steady_clock::now(); bool done = false;
+        for (uint32_t spins = 0; !(done = (*flag == seq)); spins++)
+            if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) break;
+        if (!done) HIPCHK(c, sync_stream(st));
+        std::atomic_thread_fence(std::memory_order_acquire);
+        auto sealed = [&]() { const volatile LogicPublished *q = c->h_logic; return q->seal == logic_seal(q->n, seq); };
+        if (!sealed()) {                                                      // (counted, asserted to be 0 by the tests)
+            c->n_seal_waits++;
+            const auto t1 = std::chrono::steady_clock::now();
+            while (!sealed() && std::chrono::steady_clock::now() - t1 < std::chrono::microseconds(500)) {}
+            if (!sealed()) { c->n_sync_fallbacks++; HIPCHK(c, sync_stream(st)); std::atomic_thread_fence(std::memory_order_acquire); }
+        }
+        nrec = c->h_logic->n;
+    }
+    if (nrec > c->logic_n) return c->fail(RE_E_HIP, "re_logic_list: %u records from %u listed rows", nrec, c->logic_n);
+    const uint32_t nw = std::min(nrec, capacity);
+    if (nw) HIPCHK(c, hipMemcpy(calls, c->d_logic_out.p, (size_t)nw * sizeof(re_logic_call), hipMemcpyDeviceToHost));
+    if (n_total) *n_total = nrec;
+    return RE_OK;
+} RE_ABI_GUARD(c, "re_logic_list")

@@ -254,6 +254,51 @@ __global__ void k_col_pairs(ColHeader *hdr, const ColMoved *moved, uint32_t move
                             uint2 *pairs, uint32_t pair_cap);
 __global__ void k_col_clear(const ColHeader *hdr, const ColMoved *moved, uint32_t moved_cap, uint8_t *row_moved, unsigned long long *tab_key, unsigned long long *tab_min,
                             ColHeader *h_hdr, uint32_t call);
+// entity-logic call list (re_logic.hip)
+// How often LogicFlow::update_logic (flows/logic_flow.rs:662-734, find_always_execute_entities :801-837) hands the entity of a row to
+// apply_entity_logic in the frame of *P: 0, 1 or 2.  This is the predicate of k_tick (re_kernels.hip, "the visibility gate") and of
+// k_col_moved (re_collide.hip), which spell it out themselves, without their component filters: fl = the row's flag word, rc = its
+// row_cell word.
+//   unique section, stamped by this frame's cull, entity not static: the section's listings in visible_sections_vec (stamp & 3);
+//   unique section, not stamped, RE_F_ALWAYS_EXEC: 1;
+//   shared section: 1 when the entity is not static, some linked section is stamped and not a static section, and the shared AABB is in
+//   view of the logic or the render culler -- or when the entity is RE_F_ALWAYS_EXEC and no linked section is stamped.
+__device__ __forceinline__ uint32_t logic_gate_times(uint32_t fl, uint32_t rc, const uint32_t *__restrict__ cell_stamp, const uint8_t *__restrict__ cell_flags,
+                                                     const int32_t *__restrict__ sh_cells, const Aabb *__restrict__ sh_aabb, const FrameParams &P) {
+    if ((fl & (F_DEAD | F_PHANTOM)) || rc == ROW_CELL_NONE) return 0u;
+    if (!(rc & ROW_CELL_SHARED)) {
+        const uint32_t stamp = cell_stamp[rc];
+        const bool vis = (stamp >> 2) == P.frame;
+        if (!(fl & F_STATIC) && vis) return stamp & 3u;
+        return ((fl & F_ALWAYS_EXEC) && !vis) ? 1u : 0u;
+    }
+    const uint32_t s = rc & ~ROW_CELL_SHARED;
+    // two round trips instead of up to 24 dependent ones: the eight links and the AABB, then the links' stamps and section flags (an empty link reads slot 0 and is ignored)
+    const int4 lo = reinterpret_cast<const int4 *>(sh_cells)[s * 2u], hi = reinterpret_cast<const int4 *>(sh_cells)[s * 2u + 1u];
+    const Aabb sa = sh_aabb[s];
+    const int32_t link[8] = { lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w };
+    uint32_t stamp[8], cflags[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) { const uint32_t c = link[k] >= 0 ? (uint32_t)link[k] : 0u; stamp[k] = cell_stamp[c]; cflags[k] = cell_flags[c]; }
+    bool anyvis = false, act = false;
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+        if (link[k] >= 0 && (stamp[k] >> 2) == P.frame) { anyvis = true; if (!(cflags[k] & CF_STATIC_SECTION)) act = true; }
+    bool inview = false;
+    if (act && !(fl & F_STATIC)) inview = logic_aabb_in_view(P.lookahead, P.cam[0], P.cam[1], P.cam[2], sa) || frustum_aabb_visible(P.planes, sa);
+    return ((!(fl & F_STATIC) && act && inview) || ((fl & F_ALWAYS_EXEC) && !anyvis)) ? 1u : 0u;
+}
+constexpr uint32_t LOGIC_TICKET_SHARDS = 32, LOGIC_LINE_WORDS = 32;      // counters 128 bytes apart (atomics serialise per 128-byte line)
+struct LogicHeader {                       // device block of k_logic_list; all zero between calls (the publishing workgroup clears what the call used)
+    uint32_t count, pad0[LOGIC_LINE_WORDS - 1];                          // records reserved so far: a line of its own
+    uint32_t top, pad1[LOGIC_LINE_WORDS - 1];                            // completed sign-off shards
+    uint32_t shard[LOGIC_TICKET_SHARDS * LOGIC_LINE_WORDS];              // shard[k * LINE_WORDS]: workgroups with index k modulo 32 that have signed off
+};
+struct LogicPublished { uint32_t n, seal, seq, pad; };                  // mapped host memory: the record count, its seal, and the call's sequence number (written last, publish_to_host)
+RE_HD uint32_t logic_seal(uint32_t n, uint32_t seq) { return table_word_hash(n, 1u) ^ table_word_hash(seq, 2u); }
+__global__ void k_logic_list(uint32_t n, const uint32_t *rows, const uint32_t *words, const uint32_t *row_flags, const uint32_t *row_id, const uint32_t *row_cell,
+                             const uint32_t *cell_stamp, const uint8_t *cell_flags, const int32_t *sh_cells, const Aabb *sh_aabb, const FrameParams *P,
+                             LogicHeader *hdr, unsigned long long *out, LogicPublished *h_pub, uint32_t seq);
 struct WriteOp { uint32_t comp, index; uint32_t v[4]; };
 constexpr uint32_t WRITE_GCLASS = 101;    // v[0] = group class of the row (0xFFFFFFFF hides it from the pack)
 constexpr uint32_t WRITE_FLAGS = 100;     // v[0] = and-mask, v[1] = or-mask, v[2] != 0: also retire the row's group class (entity removed)

@@ -343,6 +343,46 @@ class Pipeline:
         self._check(self._L.re_collide(self._h, 0, pairs.ctypes.data, capacity, C.byref(n)), "re_collide")
         return pairs[:min(n.value, capacity)].copy(), n.value
 
+    # -- entity logic: LogicFlow::update_logic (flows/logic_flow.rs:245) up to the callbacks ---------------
+    def set_entity_types(self, ids, type_identifiers):
+        """ECS::write_entity_type for each id (one TypeIdentifier, a 64-bit number, per id); type_identifiers=None is remove_entity_type"""
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        if type_identifiers is None:
+            ptr = None
+        else:
+            types = np.ascontiguousarray(type_identifiers, np.uint64).reshape(-1)
+            if len(types) != len(ids):
+                raise ValueError("one type identifier per entity id")
+            ptr = types.ctypes.data
+        self._check(self._L.re_set_entity_types(self._h, ids.ctypes.data, len(ids), ptr), "re_set_entity_types")
+
+    def get_entity_type(self, entity_id):
+        """ECS::get_entity_type: the TypeIdentifier of the entity, or None"""
+        t = C.c_uint64()
+        rc = self._L.re_get_entity_type(self._h, int(entity_id), C.byref(t))
+        if rc == -1:                                       # RE_E_ARG == None
+            return None
+        self._check(rc, "re_get_entity_type")
+        return t.value
+
+    def set_entity_logic(self, table):
+        """InstanceLogic::entity_logic / random_entity_logic: [(type_identifier, which)] with which = LOGIC_ENTITY | LOGIC_RANDOM bits; replaces the table"""
+        arr = (_capi.EntityLogic * max(len(table), 1))()
+        for i, (t, which) in enumerate(table):
+            arr[i].type_identifier = int(t); arr[i].which = int(which)
+        self._check(self._L.re_set_entity_logic(self._h, arr, len(table)), "re_set_entity_logic")
+
+    def logic_calls(self, capacity=None):
+        """the frame's entity-logic call list, between cull_and_pack (and collide) and tick: (records, n_total) with records a LOGIC_CALL_DT array
+        (entity_id, logic_index into the table, which, times) in no particular order"""
+        n = C.c_uint32()
+        if capacity is None:
+            self._check(self._L.re_logic_list(self._h, 0, None, 0, C.byref(n)), "re_logic_list")
+            capacity = n.value
+        rec = np.zeros(max(capacity, 1), _capi.LOGIC_CALL_DT)
+        self._check(self._L.re_logic_list(self._h, 0, rec.ctypes.data, capacity, C.byref(n)), "re_logic_list")
+        return rec[:min(n.value, capacity)].copy(), n.value
+
     # -- multi-GPU exchange (RCCL behind the C ABI) ---------------------------------------------------
     @staticmethod
     def comm_unique_id():
