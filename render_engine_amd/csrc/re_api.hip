@@ -142,7 +142,7 @@ struct re_ctx {
     DevBuf<uint32_t> d_cell_nghost; std::vector<uint32_t> h_cell_ng;
     // collision broad phase (re_collide): lists allocated at the first call
     uint32_t user_row = ROW_CELL_NONE; DevBuf<ColHeader> d_col_hdr; DevBuf<ColRegion> d_col_region; DevBuf<uint32_t> d_col_high; DevBuf<ColShared> d_col_shared; DevBuf<ColMoved> d_col_moved; DevBuf<ColNear> d_col_near; ColHeader *h_col = nullptr, *d_hcol = nullptr; uint32_t col_calls = 0;
-    DevBuf<uint8_t> d_row_moved; DevBuf<unsigned long long> d_col_tab; DevBuf<uint2> d_col_pairs; uint32_t col_moved_cap = 0, col_tab_size = 0, col_pair_cap = 0;
+    DevBuf<uint8_t> d_row_moved; DevBuf<unsigned long long> d_col_tab; DevBuf<uint2> d_col_pairs; uint32_t col_moved_cap = 0, col_tab_size = 0, col_pair_cap = 0, col_rows = 0;
     DevBuf<HashEntry> d_htab; uint32_t htab_mask = 0, htab_keys = 0; uint32_t probe_frames = 0;   // RE_CFG_PROBE: key -> slot table of the probe path (k_probe_cull)
     std::set<uint64_t> dormant_cached;                  // sections with ghosts that were cached when they were emptied: the reference's cache entry outlives the section and shows again when the section is re-created
     std::set<uint32_t> h_uncached;                       // rows made static after the static render cache froze: in the tree's static sets, not drawn
@@ -3193,11 +3193,14 @@ extern "C" int re_collide(re_ctx *c, uint32_t flags, re_collision *pairs, uint32
         HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&c->d_hcol), c->h_col, 0));
     }
     if (!c->col_moved_cap) {
-        c->col_moved_cap = (uint32_t)std::min<uint64_t>(((uint64_t)c->ndyn + 1u) * 8u, 1u << 20);
+        // by the capacities, not the counts in use: rows and dynamic slots are added within the slack of ensure_row_capacity /
+        // ensure_dyn_capacity without a reset of this scratch; both reset it where they grow (+1: the user entity)
+        c->col_rows = std::max(std::max(c->row_cap, c->n), 1u);
+        c->col_moved_cap = (uint32_t)std::min<uint64_t>(((uint64_t)std::max(c->dyn_cap, c->ndyn) + 1u) * 8u, 1u << 20);
         c->col_tab_size = 64; while (c->col_tab_size < 2u * c->col_moved_cap) c->col_tab_size <<= 1;
-        HIPCHK(c, c->d_col_moved.alloc(c->col_moved_cap, nullptr)); HIPCHK(c, c->d_col_tab.alloc((size_t)c->col_tab_size * 2, nullptr)); HIPCHK(c, c->d_row_moved.alloc(std::max(c->n, 1u), nullptr));
+        HIPCHK(c, c->d_col_moved.alloc(c->col_moved_cap, nullptr)); HIPCHK(c, c->d_col_tab.alloc((size_t)c->col_tab_size * 2, nullptr)); HIPCHK(c, c->d_row_moved.alloc(c->col_rows, nullptr));
         // cleared once; every call leaves them clean again (k_col_clear)
-        HIPCHK(c, hipMemsetAsync(c->d_row_moved.p, 0, std::max(c->n, 1u), c->stream)); HIPCHK(c, hipMemsetAsync(c->d_col_tab.p, 0xFF, (size_t)c->col_tab_size * 16, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->d_row_moved.p, 0, c->col_rows, c->stream)); HIPCHK(c, hipMemsetAsync(c->d_col_tab.p, 0xFF, (size_t)c->col_tab_size * 16, c->stream));
     }
     const uint32_t want = std::max(capacity, 1u << 12);
     if (want > c->col_pair_cap) { c->d_col_pairs.release(nullptr); HIPCHK(c, c->d_col_pairs.alloc(want, nullptr)); c->col_pair_cap = want; }
@@ -3240,7 +3243,7 @@ extern "C" int re_collide(re_ctx *c, uint32_t flags, re_collision *pairs, uint32
     if (h.n_region > COL_REGION_CAP || h.n_high > COL_REGION_CAP) return c->fail(RE_E_CAPACITY, "re_collide: %u world sections around the camera exceed the region list (%u)", h.n_region, COL_REGION_CAP);
     if (h.n_shared > COL_SHARED_CAP) return c->fail(RE_E_CAPACITY, "re_collide: %u shared sections within the collision distance exceed the list (%u)", h.n_shared, COL_SHARED_CAP);
     if (h.n_moved > c->col_moved_cap) {                                     // entries beyond the list were not cleaned up by k_col_clear
-        HIPCHK(c, hipMemset(c->d_row_moved.p, 0, std::max(c->n, 1u))); HIPCHK(c, hipMemset(c->d_col_tab.p, 0xFF, (size_t)c->col_tab_size * 16));
+        HIPCHK(c, hipMemset(c->d_row_moved.p, 0, c->col_rows)); HIPCHK(c, hipMemset(c->d_col_tab.p, 0xFF, (size_t)c->col_tab_size * 16));
     }
     if (h.n_moved > c->col_moved_cap) return c->fail(RE_E_CAPACITY, "re_collide: %u (section, moved entity) entries exceed the list (%u)", h.n_moved, c->col_moved_cap);
     const uint32_t nw = std::min(std::min(h.n_pairs, capacity), c->col_pair_cap);

@@ -334,13 +334,14 @@ class Pipeline:
 
     def collide(self, capacity=None):
         """LogicFlow::handle_collisions (flows/logic_flow.rs:452-651) of the frame, between cull_and_pack and tick: array [n, 2] of
-        the (this_entity, other_entity) arguments of every collision-logic invocation, in no particular order"""
+        the (this_entity, other_entity) arguments of every collision-logic invocation, in no particular order.  capacity=None: two
+        calls, the first asks for the total; capacity=0: one call without a buffer, which returns the total alone"""
         n = C.c_uint32()
         if capacity is None:
             self._check(self._L.re_collide(self._h, 0, None, 0, C.byref(n)), "re_collide")
             capacity = n.value
         pairs = np.zeros((max(capacity, 1), 2), np.uint32)
-        self._check(self._L.re_collide(self._h, 0, pairs.ctypes.data, capacity, C.byref(n)), "re_collide")
+        self._check(self._L.re_collide(self._h, 0, pairs.ctypes.data if capacity else None, capacity, C.byref(n)), "re_collide")
         return pairs[:min(n.value, capacity)].copy(), n.value
 
     # -- entity logic: LogicFlow::update_logic (flows/logic_flow.rs:245) up to the callbacks ---------------
