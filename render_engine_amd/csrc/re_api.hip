@@ -22,6 +22,7 @@
 #include "re_guard.h"
 #include "re_kernels.h"
 #include "re_math.h"
+#include "re_wait.h"
 #include "re_world_lights.h"
 
 using namespace re;
@@ -64,9 +65,17 @@ struct Carry {
 
 constexpr uint32_t NUM_FRAME_HEADERS = 3;   // see frame_header()
 struct re_ctx;
+static void build_plan_table(re_ctx *c);
+static void note_open_slot(re_ctx *c, uint32_t slot);
+static int size_frame_buffers(re_ctx *c);
+static int issue_cull(re_ctx *c, const re_camera *cam, uint32_t flags);
 static int flush_deferred_pack(re_ctx *c);
 static int drain_other_lane(re_ctx *c);
 static void free_second_lane(re_ctx *c);
+static int finish_tick(re_ctx *c, re_tick_result *out);
+static int resolve(re_ctx *c);
+static ShTable sh_table(re_ctx *c);
+static int sync_shared_mirrors(re_ctx *c);
 static void comm_release(re_ctx *c);
 struct re_ctx {
     re_config cfg{};
@@ -293,6 +302,7 @@ struct IssueClock {
 };
 IssueClock g_issue_clock;
 }
+static const bool g_time_rebucket = getenv("RE_EXP_TIME_REBUCKET") != nullptr;   // RE_EXP_TIME_REBUCKET=1: the phases of every re-bucket and section patch, on stderr
 static void report_issue_clock() { g_issue_clock.report(); g_issue_clock.n = 0; g_issue_clock.params = g_issue_clock.spans = g_issue_clock.scan = g_issue_clock.pack = g_issue_clock.wait = g_issue_clock.finish = 0; }
 
 // Everything the kernels publish to the polling host thread lives in ONE block of mapped, coherent pinned host memory per frame lane
@@ -443,8 +453,6 @@ static int ensure_shared_capacity(re_ctx *c, uint32_t need) {
     c->sh_cap = cap; c->rb_sh_dirty = true;
     return RE_OK;
 }
-static void build_plan_table(re_ctx *c);
-static void note_open_slot(re_ctx *c, uint32_t slot);
 static int build_sections(re_ctx *c, const std::vector<uint64_t> &row_key, const std::vector<uint8_t> &row_nk, std::vector<SharedRec> &shrec,
                           const std::vector<uint32_t> &flags, const Carry *carry = nullptr) {
     const uint32_t n = c->n;
@@ -696,8 +704,6 @@ static int build_sections(re_ctx *c, const std::vector<uint64_t> &row_key, const
     return RE_OK;
 }
 
-static int resolve(re_ctx *c);
-static int size_frame_buffers(re_ctx *c);
 // device tables of the per-model level-of-view bands: table 0 = "default bands", table t >= 1 = custom_lod[t - 1]; one table index per group class
 static int upload_lod_tables(re_ctx *c) {
     c->lod_tables_on = false;
@@ -1112,9 +1118,6 @@ static void make_frame_params(re_ctx *c, const re_camera *cam, uint32_t flags) {
     fill_union_boxes32(c->PB32.box, P.box[0], P.box[1], c->maxlevel);
 }
 
-static int finish_tick(re_ctx *c, re_tick_result *out);
-static int resolve(re_ctx *c);
-
 static void fill_visible(re_ctx *c, re_visible *out) {
     const HostResult &h = *c->h_res;
     uint32_t cap = c->ext_out_ids ? c->ext_out_cap : c->out_cap;
@@ -1206,7 +1209,6 @@ static int launch_pack_large(re_ctx *c, FrameHeader *hdr, FrameHeader *hdr_next,
     return RE_OK;
 }
 
-static int issue_cull(re_ctx *c, const re_camera *cam, uint32_t flags);
 static int finish_cull(re_ctx *c, re_visible *out) {
     { int rc = drain_other_lane(c); if (rc != RE_OK) return rc; }
     { int rc = flush_deferred_pack(c); if (rc != RE_OK) return rc; }
@@ -1217,11 +1219,8 @@ static int finish_cull(re_ctx *c, re_visible *out) {
     bool done = false;
     const double t_wait0 = g_issue_clock.on ? IssueClock::now() : 0.0;
     if (!(c->tick_inflight && c->ndyn)) {
-        const volatile uint32_t *flag = &c->h_res->done_frame;
-        const auto t0 = std::chrono::steady_clock::now();
-        for (uint32_t spins = 0; !(done = (*flag == c->frame)); spins++)
-            if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;   // long frame: let the driver wait
-        if (done) { std::atomic_thread_fence(std::memory_order_acquire); if (c->h_res->overflow == 2u || (c->h_spec && c->h_spec->stale)) done = false; else c->pending.clear(); }
+        done = poll_word(&c->h_res->done_frame, c->frame, std::chrono::milliseconds(2));   // (a longer frame: let the driver wait)
+        if (done) { if (c->h_res->overflow == 2u || (c->h_spec && c->h_spec->stale)) done = false; else c->pending.clear(); }
     }
     if (!done) { int rc = resolve(c); if (rc != RE_OK) return rc; }
     const double t_wait1 = g_issue_clock.on ? IssueClock::now() : 0.0; g_issue_clock.wait += t_wait1 - t_wait0;
@@ -1263,14 +1262,10 @@ static int finish_cull(re_ctx *c, re_visible *out) {
             if (hr->table_hash && result_seal(hsh | 1u, c->frame, hr->n_groups, hr->total, hr->n_vis_map, hr->n_vis_vec, hr->n_items) != hr->table_hash) return false;
             return n == hr->total;
         };
-        if (!table_ok()) {
-            c->n_seal_waits++;
-            const auto t0 = std::chrono::steady_clock::now();
-            bool ok = false;
-            while (!(ok = table_ok()) && std::chrono::steady_clock::now() - t0 < std::chrono::microseconds(200)) {}
-            if (!ok) { c->n_sync_fallbacks++; HIPCHK(c, sync_stream(c->stream)); std::atomic_thread_fence(std::memory_order_acquire); ok = table_ok(); }
-            if (!ok) return c->fail(RE_E_STATE, "group table inconsistent with its seal (frame %u, %u groups, %u instances)", c->frame, c->h_res->n_groups, c->h_res->total);
-        }
+        int rc = RE_OK; auto sync = [&]() -> int { HIPCHK(c, sync_stream(c->stream)); return RE_OK; };
+        const Seal seal = settle_seal(table_ok, std::chrono::microseconds(200), c->n_seal_waits, c->n_sync_fallbacks, [&] { rc = sync(); });
+        if (rc != RE_OK) return rc;
+        if (seal == Seal::never) return c->fail(RE_E_STATE, "group table inconsistent with its seal (frame %u, %u groups, %u instances)", c->frame, c->h_res->n_groups, c->h_res->total);
         if (c->h_res->n_items > c->h_res->total + c->n_dead + (uint32_t)c->h_uncached.size() + 2u * c->n_phantom) return c->fail(RE_E_CAPACITY, "instance-list segment overflow (%u reserved, %u packed)", c->h_res->n_items, c->h_res->total);
     }
     if (c->h_res->n_items > c->item_cap) return c->fail(RE_E_CAPACITY, "instance expansion capacity exceeded (%u > %u)", c->h_res->n_items, c->item_cap);
@@ -1320,7 +1315,6 @@ static void free_second_lane(re_ctx *c) {
     k.h_res = nullptr; k.d_hres = nullptr; k.h_ranges = nullptr; k.d_hranges = nullptr;
     k.deferred_pack = false; k.busy = false; c->park_ready = false;
 }
-static int flush_deferred_pack(re_ctx *c);
 // Everything except the alternating frames themselves works on one lane: send the other lane's pending pack off and wait for its stream.
 // The current lane holds the newest frame (lanes are switched before a frame is issued), so results, stamps and frame parameters
 // of "the last frame" are those of the current lane afterwards.
@@ -1507,7 +1501,6 @@ static int issue_cull(re_ctx *c, const re_camera *cam, uint32_t flags) {
     return RE_OK;
 }
 
-static int resolve(re_ctx *c);
 extern "C" int re_cull_pack(re_ctx *c, const re_camera *cam, uint32_t flags, re_visible *out) try {
     if (!c) return RE_E_ARG;
     if (!cam) return c->fail(RE_E_ARG, "re_cull_pack: camera is NULL");
@@ -1561,8 +1554,7 @@ static int32_t find_slot(const re_ctx *c, uint64_t key) {
 // ------------------------------------------------------------------------------------------------
 static int patch_sections(re_ctx *c, const Carry &carry, const std::map<uint64_t, std::vector<uint32_t>> &arrive, const std::vector<uint32_t> &removed_rows) {
     hipStream_t st = c->stream;
-    static const bool timing = getenv("RE_EXP_TIME_REBUCKET") != nullptr;
-    auto t_begin = std::chrono::steady_clock::now(); auto lap = [&](const char *what) { if (timing) { auto t = std::chrono::steady_clock::now(); fprintf(stderr, "    patch %-10s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_begin).count()); t_begin = t; } };
+    auto t_begin = std::chrono::steady_clock::now(); auto lap = [&](const char *what) { if (g_time_rebucket) { auto t = std::chrono::steady_clock::now(); fprintf(stderr, "    patch %-10s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_begin).count()); t_begin = t; } };
     auto is_pad = [](uint64_t k) { return (k & 0xFFFFFFFFFFFFull) == 0xFFFFFFFFFFFFull; };
     auto by_id = [&](uint32_t a, uint32_t b) { return c->h_id[a] < c->h_id[b]; };
     // find_slot costs ~0.25 us a call (a hash probe + a two-level search that misses the cache in the 80 MB key array) and a patch asks for the slot of
@@ -1859,8 +1851,6 @@ static RbCells rb_cells(re_ctx *c) {
 static RbTables rb_tables(re_ctx *c) { RbTables T; T.base_keys = c->d_base_keys.p; T.nbase = (uint32_t)c->base_keys.size(); T.ovl_keys = c->d_ovl_keys.p; T.ovl_slots = c->d_ovl_slots.p; T.ovl_mask = c->ovl_cap - 1u; return T; }
 
 // host mirrors of the sections the device patched, fetched when a host path needs them
-static ShTable sh_table(re_ctx *c);
-static int sync_shared_mirrors(re_ctx *c);
 static int sync_mirrors(re_ctx *c) {
     { int rc = sync_shared_mirrors(c); if (rc != RE_OK) return rc; }          // (first: a row that moved from a shared to a unique section ends as the unique part below leaves it)
     if (c->stale_slots.empty()) return RE_OK;
@@ -2003,8 +1993,7 @@ static int rebucket_on_device2(re_ctx *c, uint32_t M, std::vector<uint32_t> *hos
     host_list->clear();
     if (!M || !device_rebucket_applicable(c)) return 1;
     hipStream_t st = c->stream;
-    static const bool timing = getenv("RE_EXP_TIME_REBUCKET") != nullptr;
-    auto t_begin = std::chrono::steady_clock::now(); auto lap = [&](const char *what) { if (timing) { auto t = std::chrono::steady_clock::now(); fprintf(stderr, "  device rebucket %-10s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_begin).count()); t_begin = t; } };
+    auto t_begin = std::chrono::steady_clock::now(); auto lap = [&](const char *what) { if (g_time_rebucket) { auto t = std::chrono::steady_clock::now(); fprintf(stderr, "  device rebucket %-10s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_begin).count()); t_begin = t; } };
     // ---- lookup tables: sorted keys of the last full build + overlay of the sections created since; the shared table's device-only parts
     if (c->rb_base_dirty) {
         HIPCHK(c, c->d_base_keys.alloc(c->base_keys.size(), &c->dev_bytes));
@@ -2068,11 +2057,10 @@ static int rebucket_on_device2(re_ctx *c, uint32_t M, std::vector<uint32_t> *hos
     // the status block as the kernels so far left it: published into the mapped block by one small kernel and polled (a copy plus a stream synchronise costs ~15 us more, three times a batch)
     auto wait_status = [&](uint32_t seq) -> int {
         HIPCHK(c, hipGetLastError());
-        const volatile uint32_t *flag = B.h_seq; bool done = false;
-        const auto t0 = std::chrono::steady_clock::now();
-        for (uint32_t spins = 0; !(done = (*flag == seq)); spins++)
-            if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) break;   // a long batch: let the driver wait
-        if (!done) { HIPCHK(c, sync_stream(st)); if (*flag != seq) return c->fail(RE_E_STATE, "device re-bucket: the status block was not published"); }
+        const volatile uint32_t *flag = B.h_seq;
+        if (poll_word(flag, seq, std::chrono::milliseconds(5))) return RE_OK;
+        HIPCHK(c, sync_stream(st));                                            // a long batch: let the driver wait
+        if (*flag != seq) return c->fail(RE_E_STATE, "device re-bucket: the status block was not published");
         std::atomic_thread_fence(std::memory_order_acquire);
         return RE_OK;
     };
@@ -2257,8 +2245,7 @@ static int rebucket_on_device2(re_ctx *c, uint32_t M, std::vector<uint32_t> *hos
 struct TreeOp { uint32_t row; uint8_t kind; };                          // kind: 1 = make static, 2 = wake up, 3 = remove, 4 = add (an entity of this batch: re_ctx::add_keys holds its section decision)
 static int rebucket(re_ctx *c, uint32_t n_movers, const std::vector<TreeOp> *pre = nullptr, const std::set<uint64_t> *ghost_touched = nullptr) {
     hipStream_t st = c->stream;
-    static const bool timing = getenv("RE_EXP_TIME_REBUCKET") != nullptr;
-    auto t_begin = std::chrono::steady_clock::now(); auto lap = [&](const char *what) { if (timing) { auto t = std::chrono::steady_clock::now(); fprintf(stderr, "  rebucket %-10s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_begin).count()); t_begin = t; } };
+    auto t_begin = std::chrono::steady_clock::now(); auto lap = [&](const char *what) { if (g_time_rebucket) { auto t = std::chrono::steady_clock::now(); fprintf(stderr, "  rebucket %-10s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_begin).count()); t_begin = t; } };
     if (n_movers > c->list_cap) return c->fail(RE_E_CAPACITY, "mover list overflow");
     std::vector<uint32_t> movers; bool second_batch = false;              // second_batch: the device took the movers between unique sections, these are the rest
     if (c->shard_hi && n_movers) {                                          // a sharded world: remember who moved (re_list_migrants looks at where they went)
@@ -2480,29 +2467,18 @@ static int finish_tick(re_ctx *c, re_tick_result *out) {
     // leaving the world (the stale word is raised before the counters are published) still needs resolve(): patch the tree, replay.
     bool done = false;
     if (c->tick_published && (!c->park_ready || !(c->park.busy || c->park.deferred_pack))) {
-        const volatile uint32_t *flag = &c->h_th->ticket;
-        const auto t0 = std::chrono::steady_clock::now();
-        for (uint32_t spins = 0; !(done = (*flag == c->tick_seq)); spins++)
-            if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
+        done = poll_word(&c->h_th->ticket, c->tick_seq, std::chrono::milliseconds(2));
         if (done) {
-            std::atomic_thread_fence(std::memory_order_acquire);
-            auto sealed = [&]() { const volatile TickHeader *t = c->h_th; return t->pad[0] == (table_word_hash(t->n_changed, 1u) ^ table_word_hash(t->n_rebucket, 2u) ^ table_word_hash(t->n_oob, 3u) ^ table_word_hash(c->tick_seq, 4u)); };
-            if (!sealed()) {                                                  // (does not happen with publish_to_host; counted, and asserted to be 0 by the tests)
-                c->n_seal_waits++;
-                const auto t1 = std::chrono::steady_clock::now();
-                while (!sealed() && std::chrono::steady_clock::now() - t1 < std::chrono::microseconds(200)) {}
-                if (!sealed()) c->n_sync_fallbacks++;
-            }
-            if (!sealed() || (c->h_spec && c->h_spec->stale)) done = false;
+            auto sealed = [&]() { const volatile TickHeader *t = c->h_th; return t->pad[0] == tick_seal(t->n_changed, t->n_rebucket, t->n_oob, c->tick_seq); };
+            // (a seal that does not agree at first sight does not happen with publish_to_host; counted, and asserted to be 0 by the tests.  No synchronise here: resolve() below does it)
+            if (settle_seal(sealed, std::chrono::microseconds(200), c->n_seal_waits, c->n_sync_fallbacks) == Seal::never || (c->h_spec && c->h_spec->stale)) done = false;
         }
     }
     if (!done) {
         int rc = resolve(c);
         if (rc != RE_OK) return rc;
         // (after resolve the stream has drained: the published counters are those of the last tick that ran, replays included)
-        const volatile uint32_t *flag = &c->h_th->ticket;
-        const auto t0 = std::chrono::steady_clock::now();
-        while (c->tick_published && *flag != c->tick_seq && std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(200)) {}
+        if (c->tick_published) (void)poll_word(&c->h_th->ticket, c->tick_seq, std::chrono::milliseconds(200));
     } else c->pending.clear();
     c->tick_inflight = false;
     if (c->timed_tick) { (void)hipEventSynchronize(c->ev[4]); (void)hipEventElapsedTime(&c->t_tick, c->ev[3], c->ev[4]); c->t_tick *= 1000.f; }
@@ -2708,7 +2684,6 @@ static uint32_t group_class_of(re_ctx *c, const GroupKey &gk, bool *grew) {
     c->gmap.emplace(gk, g); c->h_gkeys.push_back(gk); *grew = true;
     return g;
 }
-static int upload_lod_tables(re_ctx *c);
 static int regrow_groups(re_ctx *c) {
     uint64_t *acct = &c->dev_bytes; hipStream_t st = c->stream;
     if (c->park_ready) { (void)drain_other_lane(c); free_second_lane(c); }
@@ -3065,14 +3040,11 @@ static int apply_changes_impl(re_ctx *c, const re_change *changes, uint32_t n, c
                            reinterpret_cast<const uint32_t *>(c->d_chg + APPLY_SMALL_MAX * sizeof(WriteOp)), row_arrays(c), c->d_dyn_vel.p, c->d_dyn_acc.p, c->d_dyn_rotvel.p, c->d_dyn_rotacc.p,
                            c->d_row_cell.p, c->d_cell_key.p, c->d_sh_cells.p, c->cfg.outline_length, c->cfg.atomic_length, c->d_th.p, c->d_movers.p, c->d_oob.p, c->list_cap, c->d_hth, seq);
         HIPCHK(c, hipGetLastError());
-        const volatile TickHeader *t = c->h_th; bool ok = false;
-        const auto t0 = std::chrono::steady_clock::now();
-        for (uint32_t spins = 0; !(ok = (t->ticket == seq)); spins++)
-            if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) break;
+        const volatile TickHeader *t = c->h_th;
+        bool ok = poll_word(&t->ticket, seq, std::chrono::milliseconds(5));
         if (ok) {
-            std::atomic_thread_fence(std::memory_order_acquire);
             th.n_changed = t->n_changed; th.n_rebucket = t->n_rebucket; th.n_oob = t->n_oob;
-            ok = t->pad[0] == (table_word_hash(th.n_changed, 1u) ^ table_word_hash(th.n_rebucket, 2u) ^ table_word_hash(th.n_oob, 3u) ^ table_word_hash(seq, 4u));
+            ok = t->pad[0] == tick_seal(th.n_changed, th.n_rebucket, th.n_oob, seq);
         }
         if (!ok) {                                                              // (a slow box, or a block that did not agree with its seal at first sight: the stream's end is authoritative)
             HIPCHK(c, sync_stream(st));
@@ -3175,6 +3147,11 @@ extern "C" int re_add_entities(re_ctx *c, const re_entities *E, uint32_t *n_reje
 // logic of the entity types (CollisionFunction callbacks) stays with the caller, which gets the argument pairs.
 // ------------------------------------------------------------------------------------------------
 constexpr uint32_t COL_REGION_CAP = 1u << 16, COL_SHARED_CAP = 1u << 14;
+// what re_collide and re_logic_list wait for before they read the frame's stamps: the frame (or whatever else is pending), then the tick
+static int settle_frame(re_ctx *c) {
+    { int rc = c->cull_inflight ? finish_cull(c, nullptr) : resolve(c); if (rc != RE_OK) return rc; }
+    return c->tick_inflight ? finish_tick(c, nullptr) : RE_OK;
+}
 extern "C" int re_collide(re_ctx *c, uint32_t flags, re_collision *pairs, uint32_t capacity, uint32_t *n_total) try {
     (void)flags;
     if (!c) return RE_E_ARG;
@@ -3182,8 +3159,7 @@ extern "C" int re_collide(re_ctx *c, uint32_t flags, re_collision *pairs, uint32
     if (!c->have_cull) return c->fail(RE_E_STATE, "re_collide: the collision pass works on the visibility query of the frame; call re_cull_pack first");
     if (capacity && !pairs) return c->fail(RE_E_ARG, "re_collide: capacity without a buffer");
     HIPCHK(c, hipSetDevice(c->device));
-    { int rc = c->cull_inflight ? finish_cull(c, nullptr) : resolve(c); if (rc != RE_OK) return rc; }
-    if (c->tick_inflight) { int rc = finish_tick(c, nullptr); if (rc != RE_OK) return rc; }
+    { int rc = settle_frame(c); if (rc != RE_OK) return rc; }
     { int rc = sync_mirrors(c); if (rc != RE_OK) return rc; }
     hipStream_t st = c->stream;
     if (!c->d_col_hdr.p) {
@@ -3225,20 +3201,13 @@ extern "C" int re_collide(re_ctx *c, uint32_t flags, re_collision *pairs, uint32
     HIPCHK(c, hipGetLastError());
     ColHeader h{};
     {   // completion: poll the counts the last kernel publishes in mapped host memory (a stream synchronise costs tens of microseconds)
-        const volatile uint32_t *flag = &c->h_col->pad[1];
-        const auto t0 = std::chrono::steady_clock::now(); bool done = false;
-        for (uint32_t spins = 0; !(done = (*flag == c->col_calls)); spins++)
-            if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) break;
-        if (!done) HIPCHK(c, sync_stream(st));
-        std::atomic_thread_fence(std::memory_order_acquire);
-        auto sealed = [&]() { const volatile ColHeader *q = c->h_col; return q->pad[0] == (table_word_hash(q->n_region, 1u) ^ table_word_hash(q->n_high, 2u) ^ table_word_hash(q->n_shared, 3u) ^ table_word_hash(q->n_moved, 4u) ^ table_word_hash(q->n_pairs, 5u) ^ table_word_hash(q->n_near, 6u) ^ table_word_hash(c->col_calls, 7u)); };
-        if (!sealed()) {                                                      // (as in finish_cull: counted, asserted to be 0 by the tests)
-            c->n_seal_waits++;
-            const auto t1 = std::chrono::steady_clock::now();
-            while (!sealed() && std::chrono::steady_clock::now() - t1 < std::chrono::microseconds(500)) {}
-            if (!sealed()) { c->n_sync_fallbacks++; HIPCHK(c, sync_stream(st)); std::atomic_thread_fence(std::memory_order_acquire); }
-        }
-        h = *c->h_col;
+        auto sync = [&]() -> int { HIPCHK(c, sync_stream(st)); std::atomic_thread_fence(std::memory_order_acquire); return RE_OK; };
+        int rc = poll_word(&c->h_col->pad[1], c->col_calls, std::chrono::milliseconds(5)) ? RE_OK : sync();
+        if (rc != RE_OK) return rc;
+        auto sealed = [&]() { const volatile ColHeader *q = c->h_col; return q->pad[0] == col_seal(q->n_region, q->n_high, q->n_shared, q->n_moved, q->n_pairs, q->n_near, c->col_calls); };
+        settle_seal(sealed, std::chrono::microseconds(500), c->n_seal_waits, c->n_sync_fallbacks, [&] { rc = sync(); });   // (as in finish_cull: counted, asserted to be 0 by the tests)
+        if (rc != RE_OK) return rc;
+        h = *c->h_col;                                                        // (after the synchronise the stream's end is authoritative, whatever the seal says)
     }
     if (h.n_region > COL_REGION_CAP || h.n_high > COL_REGION_CAP) return c->fail(RE_E_CAPACITY, "re_collide: %u world sections around the camera exceed the region list (%u)", h.n_region, COL_REGION_CAP);
     if (h.n_shared > COL_SHARED_CAP) return c->fail(RE_E_CAPACITY, "re_collide: %u shared sections within the collision distance exceed the list (%u)", h.n_shared, COL_SHARED_CAP);
@@ -3399,12 +3368,8 @@ static int gather_finish(re_ctx *c, re_gathered *out) {
     if (b < 0) return c->fail(RE_E_STATE, "re_allgather_visible: no frame has been packed since re_comm_init");
     m.pending = -1;
     auto read_headers = [&]() -> int {                                       // poll the sequence word k_gather_headers publishes behind the collective
-        const volatile uint32_t *flag = m.h_hdr + (size_t)m.n * 4;
-        const auto t0 = std::chrono::steady_clock::now();
-        bool done = false;
-        for (uint32_t spins = 0; !(done = (*flag == m.hdr_seq)); spins++)
-            if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) break;   // a long collective: let the driver wait
-        if (!done) HIPCHK(c, sync_stream(c->stream));
+        if (poll_word(m.h_hdr + (size_t)m.n * 4, m.hdr_seq, std::chrono::milliseconds(5))) return RE_OK;
+        HIPCHK(c, sync_stream(c->stream));                                    // a long collective: let the driver wait
         std::atomic_thread_fence(std::memory_order_acquire);
         return RE_OK;
     };
@@ -3708,6 +3673,15 @@ extern "C" int re_set_light_information(re_ctx *c, const uint32_t *entity_ids, u
     return RE_OK;
 } RE_ABI_GUARD(c, "re_set_light_information")
 
+// the light culler of a camera: the AABB of radius far_draw around it and its candidate box per level (generate_original_culling_aabb, visible_world_flow.rs:131-145)
+static LightQuery light_query(const re_ctx *c, const re_camera *cam, uint32_t type_flag) {
+    LightQuery Q{}; const float r = cam->far_draw, wsl = (float)c->cfg.atomic_length;
+    Q.culler = Aabb{ cam->position[0] - r, cam->position[0] + r, cam->position[1] - r, cam->position[1] + r, cam->position[2] - r, cam->position[2] + r };
+    fill_level_boxes(Q.box, c->maxlevel, wsl, rmax(cam->position[0] - r, 0.0f), cam->position[0] + r, rmax(cam->position[1] - r, 0.0f), cam->position[1] + r,
+                     rmax(cam->position[2] - r, 0.0f), cam->position[2] + r);
+    Q.max_level = c->maxlevel; Q.type_flag = type_flag;
+    return Q;
+}
 // what re_lighting_set_lights_from_world needs of the world (re_world_lights.h)
 int re::world_lights_view(re_ctx *c, int device, const re_camera *cam, const uint32_t need[3], WorldLightsView *v, std::string *err, const char *who) {
     auto fail = [&](int code, const char *msg) { *err = std::string(who) + ": " + msg; return code; };
@@ -3737,12 +3711,7 @@ int re::world_lights_view(re_ctx *c, int device, const re_camera *cam, const uin
     v->stream = c->stream; v->nl = nl;
     v->light_rows = c->d_light_rows.p; v->flags = c->d_flags.p; v->row_id = c->d_id.p; v->row_cell = c->d_row_cell.p;
     v->cell_key = c->d_cell_key.p; v->cell_flags = c->d_cell_flags.p; v->sh_cells = c->d_sh_cells.p; v->pos = c->d_pos.p; v->info = c->d_li.p; v->h_info = c->h_li_col.data(); v->li_epoch = c->li_epoch;
-    const float r = cam->far_draw, wsl = (float)c->cfg.atomic_length;
-    v->Q = LightQuery{};
-    v->Q.culler = Aabb{ cam->position[0] - r, cam->position[0] + r, cam->position[1] - r, cam->position[1] + r, cam->position[2] - r, cam->position[2] + r };
-    fill_level_boxes(v->Q.box, c->maxlevel, wsl, rmax(cam->position[0] - r, 0.0f), cam->position[0] + r, rmax(cam->position[1] - r, 0.0f), cam->position[1] + r,
-                     rmax(cam->position[2] - r, 0.0f), cam->position[2] + r);   // the culler of re_visible_lights
-    v->Q.max_level = c->maxlevel; v->Q.type_flag = F_LIGHT_ANY;
+    v->Q = light_query(c, cam, F_LIGHT_ANY);
     for (int t = 0; t < 3; t++) v->complete[t] = c->li_complete[t];
     return RE_OK;
 }
@@ -3787,11 +3756,7 @@ extern "C" int re_visible_lights(re_ctx *c, const re_camera *cam, uint32_t light
     if (!nl) return RE_OK;
     { int rc_ = sync_light_rows(c); if (rc_ != RE_OK) return rc_; }
     if (c->d_light_out.n < (size_t)nl + 1) HIPCHK(c, c->d_light_out.alloc((size_t)nl + 1, nullptr));
-    LightQuery Q{}; const float r = cam->far_draw, wsl = (float)c->cfg.atomic_length;
-    Q.culler = Aabb{ cam->position[0] - r, cam->position[0] + r, cam->position[1] - r, cam->position[1] + r, cam->position[2] - r, cam->position[2] + r };
-    fill_level_boxes(Q.box, c->maxlevel, wsl, rmax(cam->position[0] - r, 0.0f), cam->position[0] + r, rmax(cam->position[1] - r, 0.0f), cam->position[1] + r,
-                     rmax(cam->position[2] - r, 0.0f), cam->position[2] + r);   // generate_original_culling_aabb (visible_world_flow.rs:131-145)
-    Q.max_level = c->maxlevel; Q.type_flag = light_type;
+    const LightQuery Q = light_query(c, cam, light_type);
     HIPCHK(c, hipMemsetAsync(c->d_light_out.p + nl, 0, 4, c->stream));
     hipLaunchKernelGGL(k_visible_lights, dim3((nl + 255) / 256), dim3(256), 0, c->stream, nl, c->d_light_rows.p, c->d_flags.p, c->d_id.p, c->d_row_cell.p, c->d_cell_key.p, c->d_cell_flags.p,
                        c->d_sh_cells.p, Q, c->d_light_out.p, nl, c->d_light_out.p + nl);
@@ -4100,8 +4065,7 @@ extern "C" int re_logic_list(re_ctx *c, uint32_t flags, re_logic_call *calls, ui
     if (!c->h_res) return c->fail(RE_E_STATE, "re_logic_list: no world uploaded");
     if (!c->have_cull) return c->fail(RE_E_STATE, "re_logic_list: the call list follows the visibility query of the frame; call re_cull_pack first");
     HIPCHK(c, hipSetDevice(c->device));
-    { int rc = c->cull_inflight ? finish_cull(c, nullptr) : resolve(c); if (rc != RE_OK) return rc; }
-    if (c->tick_inflight) { int rc = finish_tick(c, nullptr); if (rc != RE_OK) return rc; }
+    { int rc = settle_frame(c); if (rc != RE_OK) return rc; }
     { int rc = sync_logic_rows(c); if (rc != RE_OK) return rc; }
     if (n_total) *n_total = 0;
     if (!c->logic_n) return RE_OK;
@@ -4118,19 +4082,12 @@ extern "C" int re_logic_list(re_ctx *c, uint32_t flags, re_logic_call *calls, ui
     HIPCHK(c, hipGetLastError());
     uint32_t nrec = 0;
     {   // completion: poll the sequence number the last workgroup publishes in mapped host memory (as re_collide does)
-        const volatile uint32_t *flag = &c->h_logic->seq;
-        const auto t0 = std::chrono::steady_clock::now(); bool done = false;
-        for (uint32_t spins = 0; !(done = (*flag == seq)); spins++)
-            if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) break;
-        if (!done) HIPCHK(c, sync_stream(st));
-        std::atomic_thread_fence(std::memory_order_acquire);
+        auto sync = [&]() -> int { HIPCHK(c, sync_stream(st)); std::atomic_thread_fence(std::memory_order_acquire); return RE_OK; };
+        int rc = poll_word(&c->h_logic->seq, seq, std::chrono::milliseconds(5)) ? RE_OK : sync();
+        if (rc != RE_OK) return rc;
         auto sealed = [&]() { const volatile LogicPublished *q = c->h_logic; return q->seal == logic_seal(q->n, seq); };
-        if (!sealed()) {                                                      // (counted, asserted to be 0 by the tests)
-            c->n_seal_waits++;
-            const auto t1 = std::chrono::steady_clock::now();
-            while (!sealed() && std::chrono::steady_clock::now() - t1 < std::chrono::microseconds(500)) {}
-            if (!sealed()) { c->n_sync_fallbacks++; HIPCHK(c, sync_stream(st)); std::atomic_thread_fence(std::memory_order_acquire); }
-        }
+        settle_seal(sealed, std::chrono::microseconds(500), c->n_seal_waits, c->n_sync_fallbacks, [&] { rc = sync(); });   // (counted, asserted to be 0 by the tests)
+        if (rc != RE_OK) return rc;
         nrec = c->h_logic->n;
     }
     if (nrec > c->logic_n) return c->fail(RE_E_HIP, "re_logic_list: %u records from %u listed rows", nrec, c->logic_n);

@@ -296,6 +296,12 @@ struct LogicHeader {                       // device block of k_logic_list; all 
 };
 struct LogicPublished { uint32_t n, seal, seq, pad; };                  // mapped host memory: the record count, its seal, and the call's sequence number (written last, publish_to_host)
 RE_HD uint32_t logic_seal(uint32_t n, uint32_t seq) { return table_word_hash(n, 1u) ^ table_word_hash(seq, 2u); }
+RE_HD uint32_t tick_seal(uint32_t n_changed, uint32_t n_rebucket, uint32_t n_oob, uint32_t seq) {   // TickHeader::pad[0] of the host copy (tick_sign_off, k_apply_small)
+    return table_word_hash(n_changed, 1u) ^ table_word_hash(n_rebucket, 2u) ^ table_word_hash(n_oob, 3u) ^ table_word_hash(seq, 4u);
+}
+RE_HD uint32_t col_seal(uint32_t n_region, uint32_t n_high, uint32_t n_shared, uint32_t n_moved, uint32_t n_pairs, uint32_t n_near, uint32_t call) {   // ColHeader::pad[0] of the host copy (k_col_clear)
+    return table_word_hash(n_region, 1u) ^ table_word_hash(n_high, 2u) ^ table_word_hash(n_shared, 3u) ^ table_word_hash(n_moved, 4u) ^ table_word_hash(n_pairs, 5u) ^ table_word_hash(n_near, 6u) ^ table_word_hash(call, 7u);
+}
 __global__ void k_logic_list(uint32_t n, const uint32_t *rows, const uint32_t *words, const uint32_t *row_flags, const uint32_t *row_id, const uint32_t *row_cell,
                              const uint32_t *cell_stamp, const uint8_t *cell_flags, const int32_t *sh_cells, const Aabb *sh_aabb, const FrameParams *P,
                              LogicHeader *hdr, unsigned long long *out, LogicPublished *h_pub, uint32_t seq);

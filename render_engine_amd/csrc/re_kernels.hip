@@ -1629,7 +1629,7 @@ __device__ __forceinline__ void tick_sign_off(TickHeader *th, TickHeader *h_th, 
     uint32_t a = __hip_atomic_load(&th->n_changed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // (n_changed itself: the per-lane adds of a change batch, k_apply_rows)
     for (uint32_t k2 = 0; k2 < TICK_TICKET_SHARDS; k2++) a += __hip_atomic_load(&th->shard[k2 * TICK_SHARD_STRIDE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint32_t b = __hip_atomic_load(&th->n_rebucket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), c2 = __hip_atomic_load(&th->n_oob, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    h_th->n_changed = a; h_th->n_rebucket = b; h_th->n_oob = c2; h_th->pad[0] = table_word_hash(a, 1u) ^ table_word_hash(b, 2u) ^ table_word_hash(c2, 3u) ^ table_word_hash(seq, 4u);   // seal: the reader checks it
+    h_th->n_changed = a; h_th->n_rebucket = b; h_th->n_oob = c2; h_th->pad[0] = tick_seal(a, b, c2, seq);   // seal: the reader checks it
     publish_to_host(&h_th->ticket, seq);
 }
 __global__ __launch_bounds__(256) void k_tick(uint32_t ndyn, float *__restrict__ dyn_vel, const float *__restrict__ dyn_acc,
@@ -1731,7 +1731,7 @@ __global__ __launch_bounds__(256) void k_apply_small(uint32_t n_ops, const Write
     if (tid == 0) {
         const uint32_t a = __hip_atomic_load(&th->n_changed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), b = __hip_atomic_load(&th->n_rebucket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
                        c2 = __hip_atomic_load(&th->n_oob, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        h_th->n_changed = a; h_th->n_rebucket = b; h_th->n_oob = c2; h_th->pad[0] = table_word_hash(a, 1u) ^ table_word_hash(b, 2u) ^ table_word_hash(c2, 3u) ^ table_word_hash(seq, 4u);
+        h_th->n_changed = a; h_th->n_rebucket = b; h_th->n_oob = c2; h_th->pad[0] = tick_seal(a, b, c2, seq);
         publish_to_host(&h_th->ticket, seq);
     }
 }
