@@ -372,6 +372,29 @@ int re_set_entity_logic(re_ctx *ctx, const re_entity_logic *table, uint32_t n);
 typedef struct { uint32_t entity_id; uint16_t logic_index; uint8_t which, times; } re_logic_call;   /* 8 bytes */
 int re_logic_list(re_ctx *ctx, uint32_t flags /*0*/, re_logic_call *calls, uint32_t capacity, uint32_t *n_total);
 
+/* ---- tree queries for user logic: what the callbacks get instead of &BoundingBoxTree ----
+ * LogicFunction, CollisionFunction and UserInputLogicFunction (exports/logic_components.rs:14-18) are handed the tree and may ask it who is near a box
+ * (find_all_unique_world_section_ids, stored_entities_indexes, shared_section_indexes).  Here the tree lives on the device only; the question is asked for a
+ * whole batch of boxes at once: every pair (query index, entity id) such that
+ *   the entity is live and in the tree -- not removed, not a RE_F_PHANTOM halo replica (on several GPUs exactly the owner reports it), registered in a world
+ *   section; ghost instances of the frozen static render cache are no entities; entities hidden from the pack are entities and are reported --, and
+ *   its stored StaticAABB (RE_C_STATIC_AABB, unclipped) intersects the box (unclipped) by StaticAABB::intersect (world/bounding_volumes/aabb.rs:68-73):
+ *   a.min <= b.max && a.max >= b.min on each axis, closed intervals, plain f32 compares.
+ * args (NULL: no filter): only entities with (flags & need_flags) == need_flags && (flags & forbid_flags) == 0 over the RE_F_* bits of RE_C_FLAGS.
+ * Each pair is reported once (also for an entity of a shared section linked from several sections the box covers); the order is unspecified.
+ * *n_total = number of pairs; the first `capacity` (in the order they were found) are written to `hits` (host memory).
+ * Synchronous, valid at any point between calls -- after a cull, a tick, a change batch; an asynchronous cull or tick in flight is finished first -- and
+ * independent of any camera: it reads no frame stamps.
+ * RE_E_ARG (the message names the first offending box, nothing is touched): a NaN in a box, min > max on an axis, a box whose candidate world sections over all
+ * levels exceed RE_BOX_QUERY_MAX_CELLS (about 30 atomic lengths a side; a sweep of the world is re_ecs_query's job), n > RE_BOX_QUERY_MAX_QUERIES, nonzero
+ * reserved words, capacity without a buffer.  RE_E_STATE before any upload.  n == 0, or a world without entities: no pairs. */
+typedef struct { uint32_t query, entity_id; } re_box_hit;                                 /* 8 bytes */
+typedef struct { uint32_t need_flags, forbid_flags, reserved[2]; } re_box_query_args;   /* NULL = no filter; reserved must be 0 */
+#define RE_BOX_QUERY_MAX_CELLS   32768u     /* candidate cells of one query, summed over the levels */
+#define RE_BOX_QUERY_MAX_QUERIES (1u << 20)
+int re_query_boxes(re_ctx *ctx, const float *boxes6 /* [n * 6]: xmin xmax ymin ymax zmin zmax */, uint32_t n,
+                   const re_box_query_args *args, re_box_hit *hits, uint32_t capacity, uint32_t *n_total);
+
 /* ECS read-back for user logic (LogicFunction reads components through &ECS, exports/logic_components.rs:15-18).  A component the entity does not
  * carry (never written, or removed by RE_CHANGE_REMOVE_COMPONENT) yields RE_E_ARG == ECS::get_copy -> None (objects/ecs.rs:653-664). */
 int re_read_component(re_ctx *ctx, uint32_t entity_id, int component, void *dst);

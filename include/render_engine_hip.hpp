@@ -13,6 +13,7 @@
 //                                            flows/pipeline.rs:186-276, objects/ecs.rs:199-205,384-402,653-664
 //   EntityChangeRequest / EntityChangeInformation  objects/entity_change_request.rs, applied by helper_things/entity_change_helpers.rs:32-189
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
@@ -385,6 +386,20 @@ class Pipeline {
         std::vector<EntityId> ids(n);
         if (n) check(re_ecs_query(ctx_, components.data(), (uint32_t)components.size(), ids.data(), n, &n), "re_ecs_query");
         return ids;
+    }
+    // What a LogicFunction / CollisionFunction / UserInputLogicFunction reads out of its &BoundingBoxTree (exports/logic_components.rs:14-18): the entities whose
+    // StaticAABB intersects each box of a batch, as (index of the box, entity) pairs in no particular order, each once.  need_flags / forbid_flags: RE_F_* bits
+    // an entity must / must not carry.  Valid at any point between frames.
+    std::vector<re_box_hit> find_entities_in_boxes(const std::vector<StaticAABB> &boxes, uint32_t need_flags = 0u, uint32_t forbid_flags = 0u) {
+        upload_if_needed();
+        std::vector<float> b; b.reserve(boxes.size() * 6);
+        for (const StaticAABB &a : boxes) for (float v : { a.x_range.min, a.x_range.max, a.y_range.min, a.y_range.max, a.z_range.min, a.z_range.max }) b.push_back(v);
+        const re_box_query_args args{ need_flags, forbid_flags, { 0u, 0u } };
+        uint32_t n = 0; check(re_query_boxes(ctx_, b.data(), (uint32_t)boxes.size(), &args, nullptr, 0u, &n), "re_query_boxes");
+        std::vector<re_box_hit> hits(n);
+        if (n) check(re_query_boxes(ctx_, b.data(), (uint32_t)boxes.size(), &args, hits.data(), n, &n), "re_query_boxes");
+        hits.resize(std::min<size_t>(hits.size(), n));
+        return hits;
     }
     bool has_component(EntityId e, uint32_t ecs_bit) { upload_if_needed(); uint32_t bits = 0; check(re_ecs_bitset(ctx_, e, &bits), "re_ecs_bitset"); return (bits >> ecs_bit) & 1u; }   // ecs_bit: RE_ECS_BIT_*
     re_ctx *context() { upload_if_needed(); return ctx_; }

@@ -10,7 +10,7 @@ use std::ffi::CStr;
 use std::mem::MaybeUninit;
 
 /// One resident copy of the world on one GPU.
-pub struct GpuVisibleSet { ctx: *mut ReCtx, collision_pairs: Vec<ReCollision>, logic_list: Vec<ReLogicCall> }
+pub struct GpuVisibleSet { ctx: *mut ReCtx, collision_pairs: Vec<ReCollision>, logic_list: Vec<ReLogicCall>, box_hits: Vec<ReBoxHit> }
 
 // the context is driven from the render thread only (Pipeline::execute), like the flows it replaces
 unsafe impl Send for GpuVisibleSet {}
@@ -51,7 +51,7 @@ impl GpuVisibleSet {
         let mut ctx: *mut ReCtx = std::ptr::null_mut();
         let rc = unsafe { re_create(&cfg, &mut ctx) };
         if rc != RE_OK { return Err(GpuError { code: rc, message: last_error(std::ptr::null()) }); }
-        Ok(GpuVisibleSet { ctx, collision_pairs: Vec::with_capacity(4096), logic_list: Vec::with_capacity(4096) })
+        Ok(GpuVisibleSet { ctx, collision_pairs: Vec::with_capacity(4096), logic_list: Vec::with_capacity(4096), box_hits: Vec::with_capacity(4096) })
     }
 
     fn check(&self, rc: i32) -> Result<(), GpuError> {
@@ -299,6 +299,22 @@ impl GpuVisibleSet {
             self.check(rc)?;
             if n <= cap { unsafe { self.logic_list.set_len(n as usize) }; return Ok(&self.logic_list); }
             self.logic_list = Vec::with_capacity(n as usize + n as usize / 4);          // grew past the buffer: once more with room
+        }
+    }
+
+    /// What the logic callbacks get instead of `&BoundingBoxTree` (exports/logic_components.rs:14-18): the entities whose StaticAABB intersects each
+    /// box of a batch (`boxes`: 6 floats a box, xmin xmax ymin ymax zmin zmax), as (query index, entity id) pairs in no particular order, each once.
+    /// `filter`: only entities with all of `need_flags` and none of `forbid_flags` (RE_F_* bits).  Valid at any point between calls.
+    pub fn entities_in_boxes(&mut self, boxes: &[f32], filter: Option<&ReBoxQueryArgs>) -> Result<&[ReBoxHit], GpuError> {
+        assert_eq!(boxes.len() % 6, 0);
+        let args = filter.map_or(std::ptr::null(), |f| f as *const ReBoxQueryArgs);
+        loop {
+            let mut n = 0u32;
+            let cap = self.box_hits.capacity() as u32;
+            let rc = unsafe { ffi::re_query_boxes(self.ctx, boxes.as_ptr(), (boxes.len() / 6) as u32, args, self.box_hits.as_mut_ptr(), cap, &mut n) };
+            self.check(rc)?;
+            if n <= cap { unsafe { self.box_hits.set_len(n as usize) }; return Ok(&self.box_hits); }
+            self.box_hits = Vec::with_capacity(n as usize + n as usize / 4);            // more pairs than the buffer holds: once more with room
         }
     }
 

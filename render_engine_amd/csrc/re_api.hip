@@ -264,6 +264,9 @@ struct re_ctx {
     std::vector<re_entity_logic> logic_table; std::unordered_map<uint64_t, uint32_t> logic_index;   // TypeIdentifier -> table index
     DevBuf<uint32_t> d_logic_rows, d_logic_words; DevBuf<unsigned long long> d_logic_out; DevBuf<LogicHeader> d_logic_hdr; uint32_t logic_n = 0, logic_calls = 0; bool logic_dirty = true;
     LogicPublished *h_logic = nullptr, *d_hlogic = nullptr;                    // mapped host block the kernel publishes the count into
+    // tree queries (re_query_boxes): the batch travels from two pinned buffers that alternate by call into one device array; records come back through d_boxq_out
+    BoxQuery *h_boxq[2] = {}; size_t h_boxq_cap[2] = {}; uint32_t boxq_k = 0, boxq_calls = 0; DevBuf<BoxQuery> d_boxq; DevBuf<unsigned long long> d_boxq_out;
+    DevBuf<LogicHeader> d_boxq_hdr; LogicPublished *h_boxq_pub = nullptr, *d_hboxq_pub = nullptr;
 };
 
 #define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return (ctx)->fail(RE_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
@@ -387,6 +390,9 @@ extern "C" void re_destroy(re_ctx *c) try {
     if (c->h_col) { (void)hipHostFree(c->h_col); c->h_col = nullptr; }        // lives with the collision scratch lists (kept across uploads)
     if (c->h_logic) { (void)hipHostFree(c->h_logic); c->h_logic = nullptr; }
     c->d_logic_hdr.release(nullptr);
+    if (c->h_boxq_pub) { (void)hipHostFree(c->h_boxq_pub); c->h_boxq_pub = nullptr; }
+    for (int k = 0; k < 2; k++) if (c->h_boxq[k]) { (void)hipHostFree(c->h_boxq[k]); c->h_boxq[k] = nullptr; c->h_boxq_cap[k] = 0; }
+    c->d_boxq.release(nullptr); c->d_boxq_out.release(nullptr); c->d_boxq_hdr.release(nullptr);
     for (auto &ev : c->ev) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->k1_events) (void)hipEventDestroy(ev);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1989,22 +1995,25 @@ static int ensure_device_shared(re_ctx *c) {
     c->rb_sh_dirty = false; c->sh_hash_used = n - (uint32_t)c->sh_free.size();
     return RE_OK;
 }
-static int rebucket_on_device2(re_ctx *c, uint32_t M, std::vector<uint32_t> *host_list, uint32_t n_deleted = 0) {      // n_deleted: rows of a DeleteRequest behind the M movers of the list (RB2_MOVER_DELETED)
-    host_list->clear();
-    if (!M || !device_rebucket_applicable(c)) return 1;
+// key -> slot of the resident section table on the device (rb_find: the sorted keys of the last full build + the overlay of the sections created since) and the
+// device-only parts of the shared table, brought up to date when a host path has touched them.  Readers: the device re-bucket and re_query_boxes.
+// Returns RE_OK, an error, or 1 when the overlay cannot take the sections created since the last full build (grow: enlarge it instead).
+static int ensure_device_lookup(re_ctx *c, bool grow) {
     hipStream_t st = c->stream;
-    auto t_begin = std::chrono::steady_clock::now(); auto lap = [&](const char *what) { if (g_time_rebucket) { auto t = std::chrono::steady_clock::now(); fprintf(stderr, "  device rebucket %-10s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_begin).count()); t_begin = t; } };
-    // ---- lookup tables: sorted keys of the last full build + overlay of the sections created since; the shared table's device-only parts
     if (c->rb_base_dirty) {
         HIPCHK(c, c->d_base_keys.alloc(c->base_keys.size(), &c->dev_bytes));
         HIPCHK(c, hipMemcpyAsync(c->d_base_keys.p, c->base_keys.data(), c->base_keys.size() * 8, hipMemcpyHostToDevice, st));
         c->rb_base_dirty = false;
     }
     if (!c->ovl_cap) { c->ovl_cap = 1u << 17; HIPCHK(c, c->d_ovl_keys.alloc(c->ovl_cap, nullptr)); HIPCHK(c, c->d_ovl_slots.alloc(c->ovl_cap, nullptr)); c->rb_ovl_dirty = true; }
-    if (((uint64_t)c->sh_hash_used + std::min(2u * M, c->sh_cap)) * 2u > (uint64_t)c->sh_hmask + 1u) c->rb_sh_dirty = true;      // retired ids keep their hash entry: rebuild before the probes get long
     if (c->rb_ovl_dirty || c->rb_sh_dirty) { int rc = sync_mirrors(c); if (rc != RE_OK) return rc; }
     if (c->rb_ovl_dirty) {
-        if (c->extra_slots.size() * 4u > c->ovl_cap) return 1;
+        if (c->extra_slots.size() * 4u > c->ovl_cap) {
+            if (!grow) return 1;
+            HIPCHK(c, sync_stream(st));                                          // (nothing queued may still probe the old overlay)
+            while (c->extra_slots.size() * 4u > c->ovl_cap) c->ovl_cap <<= 1;
+            HIPCHK(c, c->d_ovl_keys.alloc(c->ovl_cap, nullptr)); HIPCHK(c, c->d_ovl_slots.alloc(c->ovl_cap, nullptr));
+        }
         HIPCHK(c, hipMemsetAsync(c->d_ovl_keys.p, 0xFF, (size_t)c->ovl_cap * 8, st));
         std::vector<Pair64> pr; pr.reserve(c->extra_slots.size());
         for (auto &kv : c->extra_slots) pr.push_back(Pair64{ kv.second, 0u, kv.first });
@@ -2016,7 +2025,16 @@ static int rebucket_on_device2(re_ctx *c, uint32_t M, std::vector<uint32_t> *hos
         }
         c->ovl_count = (uint32_t)c->extra_slots.size(); c->rb_ovl_dirty = false;
     }
-    { int rc = ensure_device_shared(c); if (rc != RE_OK) return rc; }
+    return ensure_device_shared(c);
+}
+static int rebucket_on_device2(re_ctx *c, uint32_t M, std::vector<uint32_t> *host_list, uint32_t n_deleted = 0) {      // n_deleted: rows of a DeleteRequest behind the M movers of the list (RB2_MOVER_DELETED)
+    host_list->clear();
+    if (!M || !device_rebucket_applicable(c)) return 1;
+    hipStream_t st = c->stream;
+    auto t_begin = std::chrono::steady_clock::now(); auto lap = [&](const char *what) { if (g_time_rebucket) { auto t = std::chrono::steady_clock::now(); fprintf(stderr, "  device rebucket %-10s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_begin).count()); t_begin = t; } };
+    // ---- lookup tables: sorted keys of the last full build + overlay of the sections created since; the shared table's device-only parts
+    if (((uint64_t)c->sh_hash_used + std::min(2u * M, c->sh_cap)) * 2u > (uint64_t)c->sh_hmask + 1u) c->rb_sh_dirty = true;      // retired ids keep their hash entry: rebuild before the probes get long
+    { int rc = ensure_device_lookup(c, false); if (rc != RE_OK) return rc; }
     if (((uint64_t)c->sh_hash_used + std::min(2u * M, c->sh_cap)) * 2u > (uint64_t)c->sh_hmask + 1u) return 1;      // (cannot happen: the hash has 4 entries per table entry and a batch creates at most as many sections as the table has free entries)
     // ---- scratch: 2 member ops per mover + up to 8 link ops per op of a shared placement
     re_ctx::Rb2Scratch &B = c->rb2;
@@ -4096,3 +4114,97 @@ extern "C" int re_logic_list(re_ctx *c, uint32_t flags, re_logic_call *calls, ui
     if (n_total) *n_total = nrec;
     return RE_OK;
 } RE_ABI_GUARD(c, "re_logic_list")
+
+// ------------------------------------------------------------------------------------------------
+// Tree queries for user logic: what a LogicFunction / CollisionFunction / UserInputLogicFunction reads out of its &BoundingBoxTree
+// (exports/logic_components.rs:14-18) -- the entities in a batch of boxes (k_box_query, re_boxquery.hip).  The tree lives on the device only.
+// ------------------------------------------------------------------------------------------------
+static_assert(sizeof(re_box_hit) == 8 && sizeof(re_box_query_args) == 16 && sizeof(BoxQuery) == 64, "record layouts of include/re_hip.h / re_kernels.h");
+// one box as the kernel gets it; the candidate cells of all levels, counted with the kernel's own arithmetic (box_level_range)
+static uint64_t make_box_query(const float *b, uint32_t outline, uint32_t atomic, uint32_t max_level, BoxQuery *q) {
+    Aabb a = { b[0], b[1], b[2], b[3], b[4], b[5] };
+    normalize_aabb(&a, (float)outline);
+    const float lo[3] = { a.xmin, a.ymin, a.zmin }, hi[3] = { a.xmax, a.ymax, a.zmax };
+    memcpy(q->box, b, sizeof q->box); q->flags = 0; q->pad[0] = q->pad[1] = 0;
+    for (int k = 0; k < 3; k++) { q->umin[k] = f2u32(lo[k]); q->umax[k] = f2u32(hi[k]); if ((float)q->umin[k] == lo[k]) q->flags |= 1u << k; }
+    uint64_t cells = 0;
+    for (uint32_t l = 0; l <= max_level; l++) {
+        uint64_t prod = 1;
+        for (int k = 0; k < 3; k++) { uint32_t l0, h0; box_level_range(q->umin[k], q->umax[k], (q->flags >> k) & 1u, atomic << l, &l0, &h0); prod *= (uint64_t)(h0 - l0 + 1u); }
+        cells += prod;
+    }
+    q->ncells = (uint32_t)std::min<uint64_t>(cells, 0xFFFFFFFFull);
+    return cells;
+}
+extern "C" int re_query_boxes(re_ctx *c, const float *boxes6, uint32_t n, const re_box_query_args *args, re_box_hit *hits, uint32_t capacity, uint32_t *n_total) try {
+    if (!c) return RE_E_ARG;
+    if (n > RE_BOX_QUERY_MAX_QUERIES) return c->fail(RE_E_ARG, "re_query_boxes: %u boxes (at most %u a call)", n, RE_BOX_QUERY_MAX_QUERIES);
+    if (n && !boxes6) return c->fail(RE_E_ARG, "re_query_boxes: boxes6 is NULL");
+    if (capacity && !hits) return c->fail(RE_E_ARG, "re_query_boxes: capacity without a buffer");
+    if (args && (args->reserved[0] || args->reserved[1])) return c->fail(RE_E_ARG, "re_query_boxes: reserved must be 0");
+    if (!c->h_res) return c->fail(RE_E_STATE, "re_query_boxes: no world uploaded");
+    if (c->cfg.outline_length > (1u << 30)) return c->fail(RE_E_UNSUPPORTED, "re_query_boxes: outline lengths beyond 2^30 are not supported (32-bit cell arithmetic)");
+    if (n_total) *n_total = 0;
+    if (n == 0) return RE_OK;
+    // the batch, checked whole before anything is touched: built in the pinned buffer that was not the last call's source
+    const uint32_t k = c->boxq_k ^= 1u;
+    if (c->h_boxq_cap[k] < n) {
+        if (c->h_boxq[k]) { (void)hipHostFree(c->h_boxq[k]); c->h_boxq[k] = nullptr; c->h_boxq_cap[k] = 0; }
+        const size_t cap = std::max<size_t>((size_t)n + n / 2, 256);
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_boxq[k]), cap * sizeof(BoxQuery), hipHostMallocDefault));
+        c->h_boxq_cap[k] = cap;
+    }
+    BoxQuery *hq = c->h_boxq[k];
+    for (uint32_t i = 0; i < n; i++) {
+        const float *b = boxes6 + (size_t)i * 6;
+        for (int a = 0; a < 3; a++) {
+            if (b[2 * a] != b[2 * a] || b[2 * a + 1] != b[2 * a + 1]) return c->fail(RE_E_ARG, "re_query_boxes: box %u has a NaN", i);
+            if (b[2 * a] > b[2 * a + 1]) return c->fail(RE_E_ARG, "re_query_boxes: box %u is inverted (min > max on an axis)", i);
+        }
+        const uint64_t cells = make_box_query(b, c->cfg.outline_length, c->cfg.atomic_length, c->maxlevel, &hq[i]);
+        if (cells > RE_BOX_QUERY_MAX_CELLS) return c->fail(RE_E_ARG, "re_query_boxes: box %u covers %llu candidate cells (at most %u; a sweep of the world is re_ecs_query's)", i, (unsigned long long)cells, RE_BOX_QUERY_MAX_CELLS);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = settle_frame(c); if (rc != RE_OK) return rc; }                  // (an asynchronous cull or tick in flight is finished first; the query reads no frame stamps)
+    if (!c->n || !c->ncells) return RE_OK;                                     // a world without rows
+    { int rc = ensure_device_lookup(c, true); if (rc != RE_OK) return rc; }
+    hipStream_t st = c->stream;
+    if (!c->d_boxq_hdr.p) {
+        HIPCHK(c, c->d_boxq_hdr.alloc(1, nullptr)); HIPCHK(c, hipMemsetAsync(c->d_boxq_hdr.p, 0, sizeof(LogicHeader), st));      // cleared once; every call leaves it clean again
+        HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_boxq_pub), sizeof(LogicPublished), hipHostMallocMapped | hipHostMallocCoherent)); memset(c->h_boxq_pub, 0, sizeof(LogicPublished));
+        HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&c->d_hboxq_pub), c->h_boxq_pub, 0));
+    }
+    const uint32_t cap_dev = (uint32_t)std::min<uint64_t>(capacity, (uint64_t)n * c->n);      // (no more pairs than queries x rows exist)
+    if (c->d_boxq.n < n || !c->d_boxq.p || c->d_boxq_out.n < cap_dev || !c->d_boxq_out.p) {      // a buffer that must grow is replaced only after the stream has drained
+        HIPCHK(c, sync_stream(st));
+        if (c->d_boxq.n < n || !c->d_boxq.p) HIPCHK(c, c->d_boxq.alloc((size_t)n + n / 2, nullptr));
+        if (c->d_boxq_out.n < cap_dev || !c->d_boxq_out.p) HIPCHK(c, c->d_boxq_out.alloc((size_t)cap_dev + cap_dev / 2, nullptr));
+    }
+    HIPCHK(c, hipMemcpyAsync(c->d_boxq.p, hq, (size_t)n * sizeof(BoxQuery), hipMemcpyHostToDevice, st));
+    BoxQueryArgs A{};
+    A.n = n; A.n_sh_chunks = c->nsh ? (c->nsh + BOXQ_THREADS - 1u) / BOXQ_THREADS : 0u;
+    A.atomic = c->cfg.atomic_length; A.max_level = c->maxlevel; A.need = args ? args->need_flags : 0u; A.forbid = args ? args->forbid_flags : 0u; A.nrows = c->n; A.capacity = cap_dev;
+    A.q = c->d_boxq.p; A.T = rb_tables(c); A.cell_key = c->d_cell_key.p; A.cell_begin = c->d_cell_begin.p; A.cell_nl = c->d_cell_nlocal.p; A.cell_ns = c->d_cell_nstatic.p; A.rows = c->d_rows.p;
+    A.row_flags = c->d_flags.p; A.row_id = c->d_id.p; A.row_cell = c->d_row_cell.p; A.row_aabb = c->d_aabb.p;
+    A.nsh = c->nsh; A.sh_keys = c->d_sh_keys.p; A.sh_nk = c->d_sh_nk.p; A.sh_begin = c->d_sh_begin.p; A.sh_nact = c->d_sh_nact.p; A.sh_nstat = c->d_sh_nstat.p;
+    const uint32_t seq = ++c->boxq_calls;
+    A.hdr = c->d_boxq_hdr.p; A.out = c->d_boxq_out.p; A.h_pub = c->d_hboxq_pub; A.seq = seq;
+    const uint32_t grid = n + A.n_sh_chunks * ((n + BOXQ_TILE - 1u) / BOXQ_TILE);
+    hipLaunchKernelGGL(k_box_query, dim3(grid), dim3(BOXQ_THREADS), 0, st, A);
+    HIPCHK(c, hipGetLastError());
+    uint32_t nrec = 0;
+    {   // completion: the sequence number the last workgroup publishes in mapped host memory (as re_logic_list waits)
+        auto sync = [&]() -> int { HIPCHK(c, sync_stream(st)); std::atomic_thread_fence(std::memory_order_acquire); return RE_OK; };
+        int rc = poll_word(&c->h_boxq_pub->seq, seq, std::chrono::milliseconds(5)) ? RE_OK : sync();
+        if (rc != RE_OK) return rc;
+        auto sealed = [&]() { const volatile LogicPublished *q = c->h_boxq_pub; return q->seal == logic_seal(q->n, seq); };
+        settle_seal(sealed, std::chrono::microseconds(500), c->n_seal_waits, c->n_sync_fallbacks, [&] { rc = sync(); });   // (counted, asserted to be 0 by the tests)
+        if (rc != RE_OK) return rc;
+        nrec = c->h_boxq_pub->n;
+    }
+    const uint32_t nw = std::min(nrec, cap_dev);
+    if (nw) HIPCHK(c, hipMemcpy(hits, c->d_boxq_out.p, (size_t)nw * sizeof(re_box_hit), hipMemcpyDeviceToHost));
+    if (n_total) *n_total = nrec;
+    return RE_OK;
+} RE_ABI_GUARD(c, "re_query_boxes")

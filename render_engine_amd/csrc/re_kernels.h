@@ -306,7 +306,7 @@ __global__ void k_logic_list(uint32_t n, const uint32_t *rows, const uint32_t *w
                              const uint32_t *cell_stamp, const uint8_t *cell_flags, const int32_t *sh_cells, const Aabb *sh_aabb, const FrameParams *P,
                              LogicHeader *hdr, unsigned long long *out, LogicPublished *h_pub, uint32_t seq);
 struct WriteOp { uint32_t comp, index; uint32_t v[4]; };
-constexpr uint32_t WRITE_GCLASS = 101;    // v[0] = group class of the row (0xFFFFFFFF hides it from the pack)
+constexpr uint32_t WRITE_GCLASS = 101;   // v[0] = group class of the row (0xFFFFFFFF hides it from the pack)
 constexpr uint32_t WRITE_FLAGS = 100;     // v[0] = and-mask, v[1] = or-mask, v[2] != 0: also retire the row's group class (entity removed)
 __global__ void k_write_components(uint32_t m, const WriteOp *ops, RowArrays R, float *dyn_vel, float *dyn_acc, float *dyn_rotvel, float *dyn_rotacc);
 constexpr uint32_t APPLY_SMALL_MAX = 256;   // component writes / moved entities of a change batch that k_apply_small takes in ONE launch of one workgroup
@@ -406,6 +406,34 @@ __device__ __forceinline__ void rb_ovl_put(const RbTables &T, uint64_t key, uint
     }
 }
 #endif
+// tree queries for user logic (re_boxquery.hip): the entities whose StaticAABB intersects each box of a batch
+// One query as the host builds it (re_query_boxes): the box as given (the exact test runs on it), and the box clipped to the world (normalize_aabb) as
+// integers -- umin / umax = the clipped bounds truncated, flags bit a = the clipped minimum of axis a (x, y, z) is a whole number.  The cell range of
+// every level follows from these by integer arithmetic alone (box_level_range), on the host (candidate count, the cap) and in the kernel alike.
+struct BoxQuery { float box[6]; uint32_t umin[3], umax[3], flags, ncells, pad[2]; };      // 64 bytes; ncells: candidate cells over all levels
+// Cells [lo, hi] of one axis at the level of section length len that can hold a section of an entity whose clipped interval meets the clipped
+// query interval.  hi is not clamped to the grid (an entity clipped to `outline` sits in cell outline / len, one past it); lo steps down by one
+// when the query minimum lies exactly on a section border, because the reference puts an entity whose maximum lies on a border into the
+// lower section only (num_sections_1d, re_math.h).
+RE_HD void box_level_range(uint32_t umin, uint32_t umax, bool whole, uint32_t len, uint32_t *lo, uint32_t *hi) {
+    uint32_t l = udiv_len(umin, len);
+    if (whole && l > 0u && l * len == umin) l -= 1u;
+    *lo = l; *hi = udiv_len(umax, len);
+}
+constexpr uint32_t BOXQ_THREADS = 256, BOXQ_PROBES = 4;      // probes a lane makes per round: 1024 candidate cells a round
+constexpr uint32_t BOXQ_QUEUE = BOXQ_THREADS * BOXQ_PROBES;   // hit sections of one round (each probe yields at most one)
+constexpr uint32_t BOXQ_HITBUF = 1024;                        // records a workgroup stages in LDS between two flushes (more go out one wave at a time)
+constexpr uint32_t BOXQ_TILE = 256;                           // queries a workgroup of the shared part tests its 256 shared sections against
+struct BoxQueryArgs {
+    uint32_t n, n_sh_chunks;                // queries; 256-entry chunks of the shared table (the grid: n workgroups, then n_sh_chunks per tile of BOXQ_TILE queries)
+    uint32_t atomic, max_level, need, forbid, nrows, capacity;
+    const BoxQuery *q;
+    RbTables T; const uint64_t *cell_key; const uint32_t *cell_begin, *cell_nl, *cell_ns, *rows;
+    const uint32_t *row_flags, *row_id, *row_cell; const Aabb *row_aabb;
+    uint32_t nsh; const uint64_t *sh_keys; const uint8_t *sh_nk; const uint32_t *sh_begin, *sh_nact, *sh_nstat;
+    LogicHeader *hdr; unsigned long long *out; LogicPublished *h_pub; uint32_t seq;      // count, sign-off and publication as k_logic_list's (a block of its own)
+};
+__global__ void k_box_query(BoxQueryArgs A);
 hipError_t sort_pairs_u64_u32(void *tmp, size_t *tmp_bytes, const uint64_t *keys_in, uint64_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out,
                               uint32_t n, unsigned begin_bit, unsigned end_bit, hipStream_t stream);      // re_sort.hip (rocPRIM radix sort)
 __global__ void k_rb_ovl_insert(uint32_t n, const Pair64 *pairs, RbTables T);

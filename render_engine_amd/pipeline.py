@@ -384,6 +384,20 @@ class Pipeline:
         self._check(self._L.re_logic_list(self._h, 0, rec.ctypes.data, capacity, C.byref(n)), "re_logic_list")
         return rec[:min(n.value, capacity)].copy(), n.value
 
+    # -- tree queries: what the logic callbacks get instead of &BoundingBoxTree ------------------------------
+    def find_entities_in_boxes(self, boxes, need_flags=0, forbid_flags=0, capacity=None):
+        """the entities whose StaticAABB intersects each box of a batch ([n, 6]: xmin xmax ymin ymax zmin zmax): (hits, n_total) with hits a BOX_HIT_DT
+        array (query, entity_id) in no particular order; need_flags / forbid_flags filter by the F_* bits of the entity.  Valid at any point between calls."""
+        boxes = np.ascontiguousarray(boxes, np.float32).reshape(-1, 6)
+        args = _capi.BoxQueryArgs(int(need_flags), int(forbid_flags)) if (need_flags or forbid_flags) else None
+        n = C.c_uint32()
+        if capacity is None:
+            self._check(self._L.re_query_boxes(self._h, boxes.ctypes.data, len(boxes), args, None, 0, C.byref(n)), "re_query_boxes")
+            capacity = n.value
+        hits = np.zeros(max(capacity, 1), _capi.BOX_HIT_DT)
+        self._check(self._L.re_query_boxes(self._h, boxes.ctypes.data, len(boxes), args, hits.ctypes.data, capacity, C.byref(n)), "re_query_boxes")
+        return hits[:min(n.value, capacity)].copy(), n.value
+
     # -- multi-GPU exchange (RCCL behind the C ABI) ---------------------------------------------------
     @staticmethod
     def comm_unique_id():
