@@ -77,6 +77,15 @@ static int resolve(re_ctx *c);
 static ShTable sh_table(re_ctx *c);
 static int sync_shared_mirrors(re_ctx *c);
 static void comm_release(re_ctx *c);
+// The host end of a record-list flow: the device header its kernel's workgroups sign off on (list_sign_off, re_kernels.h), the mapped
+// block the last of them publishes count, seal and sequence number into, and the sequence numbers of the calls.  Both live from the first call to re_destroy.
+struct ListChannel {
+    DevBuf<LogicHeader> hdr; LogicPublished *h_pub = nullptr, *d_pub = nullptr; uint32_t calls = 0;      // (d_pub: the device's address of the mapped block)
+    int open(re_ctx *c);                                   // at the first call: the header and the mapped block, both zero
+    uint32_t next_seq() { return ++calls; }
+    int wait(re_ctx *c, uint32_t seq, uint32_t *n);       // completion of call `seq`: polls the sequence number the last workgroup publishes (a stream synchronise costs tens of microseconds)
+    void close() { if (h_pub) { (void)hipHostFree(h_pub); h_pub = d_pub = nullptr; } hdr.release(nullptr); }
+};
 struct re_ctx {
     re_config cfg{};
     int device = 0;
@@ -262,11 +271,9 @@ struct re_ctx {
     // setter or an upload has marked them dirty -- moves, make-static, wake-up and deletes need no rebuild (the kernel reads the live flags, row_cell and stamps).
     std::vector<uint64_t> h_type; std::vector<uint8_t> h_typed;                // [row]; rows beyond the vectors carry no type
     std::vector<re_entity_logic> logic_table; std::unordered_map<uint64_t, uint32_t> logic_index;   // TypeIdentifier -> table index
-    DevBuf<uint32_t> d_logic_rows, d_logic_words; DevBuf<unsigned long long> d_logic_out; DevBuf<LogicHeader> d_logic_hdr; uint32_t logic_n = 0, logic_calls = 0; bool logic_dirty = true;
-    LogicPublished *h_logic = nullptr, *d_hlogic = nullptr;                    // mapped host block the kernel publishes the count into
+    DevBuf<uint32_t> d_logic_rows, d_logic_words; DevBuf<unsigned long long> d_logic_out; ListChannel logic; uint32_t logic_n = 0; bool logic_dirty = true;
     // tree queries (re_query_boxes): the batch travels from two pinned buffers that alternate by call into one device array; records come back through d_boxq_out
-    BoxQuery *h_boxq[2] = {}; size_t h_boxq_cap[2] = {}; uint32_t boxq_k = 0, boxq_calls = 0; DevBuf<BoxQuery> d_boxq; DevBuf<unsigned long long> d_boxq_out;
-    DevBuf<LogicHeader> d_boxq_hdr; LogicPublished *h_boxq_pub = nullptr, *d_hboxq_pub = nullptr;
+    BoxQuery *h_boxq[2] = {}; size_t h_boxq_cap[2] = {}; uint32_t boxq_k = 0; DevBuf<BoxQuery> d_boxq; DevBuf<unsigned long long> d_boxq_out; ListChannel boxq;
 };
 
 #define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return (ctx)->fail(RE_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
@@ -291,6 +298,20 @@ static hipError_t sync_stream(hipStream_t st) {
             if (dt > std::chrono::milliseconds(2)) std::this_thread::sleep_for(std::chrono::microseconds(50));   // a long wait (an upload, a rebuild): stop burning the core
         }
     }
+}
+
+struct StreamSync { re_ctx *c; hipStream_t st; int operator()() const { HIPCHK(c, sync_stream(st)); return RE_OK; } };      // the synchronise behind the waits of re_wait.h
+int ListChannel::open(re_ctx *c) {
+    if (hdr.p) return RE_OK;
+    HIPCHK(c, hdr.alloc(1, nullptr)); HIPCHK(c, hipMemsetAsync(hdr.p, 0, sizeof(LogicHeader), c->stream));      // cleared once; every call leaves it clean again
+    HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&h_pub), sizeof(LogicPublished), hipHostMallocMapped | hipHostMallocCoherent)); memset(h_pub, 0, sizeof(LogicPublished));
+    HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&d_pub), h_pub, 0));
+    return RE_OK;
+}
+int ListChannel::wait(re_ctx *c, uint32_t seq, uint32_t *n) {
+    auto sealed = [&]() { const volatile LogicPublished *q = h_pub; return q->seal == logic_seal(q->n, seq); };
+    { int rc = wait_sealed(&h_pub->seq, seq, std::chrono::milliseconds(5), sealed, std::chrono::microseconds(500), c->n_seal_waits, c->n_sync_fallbacks, StreamSync{ c, c->stream }); if (rc != RE_OK) return rc; }   // (counted, asserted to be 0 by the tests)
+    *n = h_pub->n; return RE_OK;
 }
 
 extern "C" uint32_t re_abi_version(void) { return 3u; }
@@ -351,12 +372,20 @@ static void release_rb2(re_ctx *c) {
     B.mnk.release(nullptr); B.tmp.release(nullptr); B.segs_u.release(nullptr); B.segs_s.release(nullptr); B.status.release(nullptr); B.cap = 0;
     if (B.pin) { (void)hipHostFree(B.pin); B.pin = nullptr; B.pin_bytes = 0; }
 }
+static void drop_collision_scratch(re_ctx *c) { c->d_row_moved.release(nullptr); c->d_col_moved.release(nullptr); c->d_col_tab.release(nullptr); c->col_moved_cap = 0; }   // sized by the row and dynamic-slot capacities: dropped where those change, sized again at the next re_collide
+// What re_collide, re_logic_list and re_query_boxes allocate lazily and keep across uploads (the logic flow's row lists and record buffer belong to the world: free_world).
+static void release_flows(re_ctx *c) {
+    c->d_col_hdr.release(nullptr); c->d_col_region.release(nullptr); c->d_col_high.release(nullptr); c->d_col_shared.release(nullptr); c->d_col_near.release(nullptr); c->d_col_pairs.release(nullptr); c->col_pair_cap = 0; drop_collision_scratch(c);
+    if (c->h_col) { (void)hipHostFree(c->h_col); c->h_col = c->d_hcol = nullptr; }
+    c->logic.close(); c->boxq.close(); c->d_boxq.release(nullptr); c->d_boxq_out.release(nullptr);
+    for (int k = 0; k < 2; k++) if (c->h_boxq[k]) { (void)hipHostFree(c->h_boxq[k]); c->h_boxq[k] = nullptr; c->h_boxq_cap[k] = 0; }
+}
 static void free_world(re_ctx *c) {
     uint64_t *a = &c->dev_bytes;
     c->d_light_rows.release(nullptr); c->d_light_out.release(nullptr); c->light_rows_dirty = true;
     c->h_li.clear(); c->h_li_col.clear(); c->d_li.release(nullptr); c->li_dirty = true;
     c->h_type.clear(); c->h_typed.clear(); c->d_logic_rows.release(nullptr); c->d_logic_words.release(nullptr); c->d_logic_out.release(nullptr); c->logic_n = 0; c->logic_dirty = true;   // (the logic table stays)
-    c->d_cell_cap.release(a); c->d_cell_links.release(a); c->h_linked_slots.clear(); c->d_base_keys.release(a); c->d_ovl_keys.release(nullptr); c->d_ovl_slots.release(nullptr); c->rb_base_dirty = c->rb_ovl_dirty = true; c->stale_slots.clear();
+    c->d_cell_cap.release(a); c->d_cell_links.release(a); c->h_linked_slots.clear(); c->d_base_keys.release(a); c->d_ovl_keys.release(nullptr); c->d_ovl_slots.release(nullptr); c->ovl_cap = 0; c->rb_base_dirty = c->rb_ovl_dirty = true; c->stale_slots.clear();
     c->d_hrb_list.release(nullptr); c->d_hrb_nk.release(nullptr); c->d_hrb_keys.release(nullptr); c->d_chg_ops.release(nullptr); c->d_chg_list.release(nullptr);
     if (c->h_chg) { (void)hipHostFree(c->h_chg); c->h_chg = nullptr; c->d_chg = nullptr; }
     c->d_sh_keys.release(nullptr); c->d_sh_nk.release(nullptr); c->d_cell_inact.release(nullptr); c->d_sh_rowcap.release(nullptr); c->d_sh_hidx.release(nullptr); c->d_sh_hkeys.release(nullptr);
@@ -387,12 +416,7 @@ extern "C" void re_destroy(re_ctx *c) try {
     if (c->stream) (void)sync_stream(c->stream);
     if (c->comm.comm) comm_release(c);
     free_world(c);
-    if (c->h_col) { (void)hipHostFree(c->h_col); c->h_col = nullptr; }        // lives with the collision scratch lists (kept across uploads)
-    if (c->h_logic) { (void)hipHostFree(c->h_logic); c->h_logic = nullptr; }
-    c->d_logic_hdr.release(nullptr);
-    if (c->h_boxq_pub) { (void)hipHostFree(c->h_boxq_pub); c->h_boxq_pub = nullptr; }
-    for (int k = 0; k < 2; k++) if (c->h_boxq[k]) { (void)hipHostFree(c->h_boxq[k]); c->h_boxq[k] = nullptr; c->h_boxq_cap[k] = 0; }
-    c->d_boxq.release(nullptr); c->d_boxq_out.release(nullptr); c->d_boxq_hdr.release(nullptr);
+    release_flows(c);
     for (auto &ev : c->ev) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->k1_events) (void)hipEventDestroy(ev);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -809,7 +833,7 @@ extern "C" int re_upload_entities(re_ctx *c, const re_entities *E, uint32_t *n_r
     c->light_rows_dirty = true;
     c->n_phantom = 0; for (uint32_t r = 0; r < n; r++) if (flags[r] & F_PHANTOM) c->n_phantom++;      // halo replicas: listed by the scan, hidden from the pack (twice each in duplicates mode)
     c->user_row = ROW_CELL_NONE; for (uint32_t r = 0; r < n; r++) if (flags[r] & F_USER) { c->user_row = r; break; }
-    c->d_row_moved.release(nullptr); c->d_col_moved.release(nullptr); c->d_col_tab.release(nullptr); c->col_moved_cap = 0;
+    drop_collision_scratch(c);
     for (uint32_t f : flags) if (f & F_HAS_ROTVEL) { c->has_rotvel = true; break; }
     c->ndyn = c->ndyn0 = c->dyn_cap = (uint32_t)dyn_row.size();
     c->ngclass = (uint32_t)gkeys.size(); c->nslots = c->ngclass * 8u; c->h_gkeys = gkeys;
@@ -2076,11 +2100,8 @@ static int rebucket_on_device2(re_ctx *c, uint32_t M, std::vector<uint32_t> *hos
     auto wait_status = [&](uint32_t seq) -> int {
         HIPCHK(c, hipGetLastError());
         const volatile uint32_t *flag = B.h_seq;
-        if (poll_word(flag, seq, std::chrono::milliseconds(5))) return RE_OK;
-        HIPCHK(c, sync_stream(st));                                            // a long batch: let the driver wait
-        if (*flag != seq) return c->fail(RE_E_STATE, "device re-bucket: the status block was not published");
-        std::atomic_thread_fence(std::memory_order_acquire);
-        return RE_OK;
+        { int rc = wait_word(flag, seq, std::chrono::milliseconds(5), StreamSync{ c, st }); if (rc != RE_OK) return rc; }      // (a long batch: the driver waits)
+        return *flag == seq ? RE_OK : c->fail(RE_E_STATE, "device re-bucket: the status block was not published");
     };
     auto read_status = [&](const void *src_a = nullptr, void *h_a = nullptr, uint32_t words_a = 0, const void *src_b = nullptr, void *h_b = nullptr, uint32_t words_b = 0, bool reset = false) -> int {
         const uint32_t seq = ++B.seq;
@@ -2665,7 +2686,7 @@ static int ensure_row_capacity(re_ctx *c, uint32_t need) {
     }
     c->row_cap = c->ghost_base = new_cap; c->ghost_cap = new_ghost_cap;
     c->last_pack.kind = 0;                                                   // (what the last pack was launched with names the old columns)
-    c->d_row_moved.release(nullptr); c->d_col_moved.release(nullptr); c->d_col_tab.release(nullptr); c->col_moved_cap = 0;   // collision scratch: sized at its next use
+    drop_collision_scratch(c);
     return size_frame_buffers(c);
 }
 static int ensure_dyn_capacity(re_ctx *c, uint32_t need) {
@@ -2676,7 +2697,7 @@ static int ensure_dyn_capacity(re_ctx *c, uint32_t need) {
     HIPCHK(c, grow_buf(c->d_dyn_row, k, new_cap, a, st)); HIPCHK(c, grow_buf(c->d_dyn_vel, (size_t)k * 3, (size_t)new_cap * 3, a, st)); HIPCHK(c, grow_buf(c->d_dyn_acc, (size_t)k * 3, (size_t)new_cap * 3, a, st));
     HIPCHK(c, grow_buf(c->d_dyn_rotvel, (size_t)k * 4, (size_t)new_cap * 4, a, st)); HIPCHK(c, grow_buf(c->d_dyn_rotacc, (size_t)k * 4, (size_t)new_cap * 4, a, st));
     c->dyn_cap = new_cap;
-    c->col_moved_cap = 0; c->d_col_moved.release(nullptr); c->d_col_tab.release(nullptr); c->d_row_moved.release(nullptr);
+    drop_collision_scratch(c);
     return size_frame_buffers(c);
 }
 // a slot of the dynamic table for a row that had none (an added entity with a velocity, or Velocity written to an entity registered without one:
@@ -3217,16 +3238,10 @@ extern "C" int re_collide(re_ctx *c, uint32_t flags, re_collision *pairs, uint32
     hipLaunchKernelGGL(k_col_clear, dim3((c->col_moved_cap + 255) / 256), dim3(256), 0, st, c->d_col_hdr.p, c->d_col_moved.p, c->col_moved_cap, c->d_row_moved.p, tab_key, tab_min,
                        c->d_hcol, ++c->col_calls);
     HIPCHK(c, hipGetLastError());
-    ColHeader h{};
-    {   // completion: poll the counts the last kernel publishes in mapped host memory (a stream synchronise costs tens of microseconds)
-        auto sync = [&]() -> int { HIPCHK(c, sync_stream(st)); std::atomic_thread_fence(std::memory_order_acquire); return RE_OK; };
-        int rc = poll_word(&c->h_col->pad[1], c->col_calls, std::chrono::milliseconds(5)) ? RE_OK : sync();
-        if (rc != RE_OK) return rc;
-        auto sealed = [&]() { const volatile ColHeader *q = c->h_col; return q->pad[0] == col_seal(q->n_region, q->n_high, q->n_shared, q->n_moved, q->n_pairs, q->n_near, c->col_calls); };
-        settle_seal(sealed, std::chrono::microseconds(500), c->n_seal_waits, c->n_sync_fallbacks, [&] { rc = sync(); });   // (as in finish_cull: counted, asserted to be 0 by the tests)
-        if (rc != RE_OK) return rc;
-        h = *c->h_col;                                                        // (after the synchronise the stream's end is authoritative, whatever the seal says)
-    }
+    // completion: poll the counts the last kernel publishes in mapped host memory (a stream synchronise costs tens of microseconds)
+    auto sealed = [&]() { const volatile ColHeader *q = c->h_col; return q->pad[0] == col_seal(q->n_region, q->n_high, q->n_shared, q->n_moved, q->n_pairs, q->n_near, c->col_calls); };
+    { int rc = wait_sealed(&c->h_col->pad[1], c->col_calls, std::chrono::milliseconds(5), sealed, std::chrono::microseconds(500), c->n_seal_waits, c->n_sync_fallbacks, StreamSync{ c, st }); if (rc != RE_OK) return rc; }   // (counted, asserted to be 0 by the tests)
+    const ColHeader h = *c->h_col;                                            // (after the synchronise the stream's end is authoritative, whatever the seal says)
     if (h.n_region > COL_REGION_CAP || h.n_high > COL_REGION_CAP) return c->fail(RE_E_CAPACITY, "re_collide: %u world sections around the camera exceed the region list (%u)", h.n_region, COL_REGION_CAP);
     if (h.n_shared > COL_SHARED_CAP) return c->fail(RE_E_CAPACITY, "re_collide: %u shared sections within the collision distance exceed the list (%u)", h.n_shared, COL_SHARED_CAP);
     if (h.n_moved > c->col_moved_cap) {                                     // entries beyond the list were not cleaned up by k_col_clear
@@ -3385,12 +3400,8 @@ static int gather_finish(re_ctx *c, re_gathered *out) {
     const int b = m.pending >= 0 ? m.pending : m.last;
     if (b < 0) return c->fail(RE_E_STATE, "re_allgather_visible: no frame has been packed since re_comm_init");
     m.pending = -1;
-    auto read_headers = [&]() -> int {                                       // poll the sequence word k_gather_headers publishes behind the collective
-        if (poll_word(m.h_hdr + (size_t)m.n * 4, m.hdr_seq, std::chrono::milliseconds(5))) return RE_OK;
-        HIPCHK(c, sync_stream(c->stream));                                    // a long collective: let the driver wait
-        std::atomic_thread_fence(std::memory_order_acquire);
-        return RE_OK;
-    };
+    // poll the sequence word k_gather_headers publishes behind the collective (a long collective: the driver waits)
+    auto read_headers = [&]() -> int { return wait_word(m.h_hdr + (size_t)m.n * 4, m.hdr_seq, std::chrono::milliseconds(5), StreamSync{ c, c->stream }); };
     { int rc = read_headers(); if (rc != RE_OK) return rc; }
     // A frame cancelled by cross-frame speculation left a marker in its slab header instead of a count (every rank reads the same headers, so every
     // rank takes this branch together): settle the speculation here -- the replay packs into the same slab -- and gather again.
@@ -4088,26 +4099,14 @@ extern "C" int re_logic_list(re_ctx *c, uint32_t flags, re_logic_call *calls, ui
     if (n_total) *n_total = 0;
     if (!c->logic_n) return RE_OK;
     hipStream_t st = c->stream;
-    if (!c->d_logic_hdr.p) {
-        HIPCHK(c, c->d_logic_hdr.alloc(1, nullptr)); HIPCHK(c, hipMemsetAsync(c->d_logic_hdr.p, 0, sizeof(LogicHeader), st));      // cleared once; every call leaves it clean again
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_logic), sizeof(LogicPublished), hipHostMallocMapped | hipHostMallocCoherent)); memset(c->h_logic, 0, sizeof(LogicPublished));
-        HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&c->d_hlogic), c->h_logic, 0));
-    }
-    const uint32_t seq = ++c->logic_calls;
+    { int rc = c->logic.open(c); if (rc != RE_OK) return rc; }
+    const uint32_t seq = c->logic.next_seq();
     hipLaunchKernelGGL(k_logic_list, dim3((c->logic_n + 255u) / 256u), dim3(256), 0, st, c->logic_n, (const uint32_t *)c->d_logic_rows.p, (const uint32_t *)c->d_logic_words.p,
                        (const uint32_t *)c->d_flags.p, (const uint32_t *)c->d_id.p, (const uint32_t *)c->d_row_cell.p, (const uint32_t *)c->d_cell_stamp.p, (const uint8_t *)c->d_cell_flags.p,
-                       (const int32_t *)c->d_sh_cells.p, (const Aabb *)c->d_sh_aabb.p, (const FrameParams *)c->d_params.p, c->d_logic_hdr.p, c->d_logic_out.p, c->d_hlogic, seq);
+                       (const int32_t *)c->d_sh_cells.p, (const Aabb *)c->d_sh_aabb.p, (const FrameParams *)c->d_params.p, c->logic.hdr.p, c->d_logic_out.p, c->logic.d_pub, seq);
     HIPCHK(c, hipGetLastError());
     uint32_t nrec = 0;
-    {   // completion: poll the sequence number the last workgroup publishes in mapped host memory (as re_collide does)
-        auto sync = [&]() -> int { HIPCHK(c, sync_stream(st)); std::atomic_thread_fence(std::memory_order_acquire); return RE_OK; };
-        int rc = poll_word(&c->h_logic->seq, seq, std::chrono::milliseconds(5)) ? RE_OK : sync();
-        if (rc != RE_OK) return rc;
-        auto sealed = [&]() { const volatile LogicPublished *q = c->h_logic; return q->seal == logic_seal(q->n, seq); };
-        settle_seal(sealed, std::chrono::microseconds(500), c->n_seal_waits, c->n_sync_fallbacks, [&] { rc = sync(); });   // (counted, asserted to be 0 by the tests)
-        if (rc != RE_OK) return rc;
-        nrec = c->h_logic->n;
-    }
+    { int rc = c->logic.wait(c, seq, &nrec); if (rc != RE_OK) return rc; }
     if (nrec > c->logic_n) return c->fail(RE_E_HIP, "re_logic_list: %u records from %u listed rows", nrec, c->logic_n);
     const uint32_t nw = std::min(nrec, capacity);
     if (nw) HIPCHK(c, hipMemcpy(calls, c->d_logic_out.p, (size_t)nw * sizeof(re_logic_call), hipMemcpyDeviceToHost));
@@ -4170,11 +4169,7 @@ extern "C" int re_query_boxes(re_ctx *c, const float *boxes6, uint32_t n, const 
     if (!c->n || !c->ncells) return RE_OK;                                     // a world without rows
     { int rc = ensure_device_lookup(c, true); if (rc != RE_OK) return rc; }
     hipStream_t st = c->stream;
-    if (!c->d_boxq_hdr.p) {
-        HIPCHK(c, c->d_boxq_hdr.alloc(1, nullptr)); HIPCHK(c, hipMemsetAsync(c->d_boxq_hdr.p, 0, sizeof(LogicHeader), st));      // cleared once; every call leaves it clean again
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_boxq_pub), sizeof(LogicPublished), hipHostMallocMapped | hipHostMallocCoherent)); memset(c->h_boxq_pub, 0, sizeof(LogicPublished));
-        HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&c->d_hboxq_pub), c->h_boxq_pub, 0));
-    }
+    { int rc = c->boxq.open(c); if (rc != RE_OK) return rc; }
     const uint32_t cap_dev = (uint32_t)std::min<uint64_t>(capacity, (uint64_t)n * c->n);      // (no more pairs than queries x rows exist)
     if (c->d_boxq.n < n || !c->d_boxq.p || c->d_boxq_out.n < cap_dev || !c->d_boxq_out.p) {      // a buffer that must grow is replaced only after the stream has drained
         HIPCHK(c, sync_stream(st));
@@ -4188,21 +4183,12 @@ extern "C" int re_query_boxes(re_ctx *c, const float *boxes6, uint32_t n, const 
     A.q = c->d_boxq.p; A.T = rb_tables(c); A.cell_key = c->d_cell_key.p; A.cell_begin = c->d_cell_begin.p; A.cell_nl = c->d_cell_nlocal.p; A.cell_ns = c->d_cell_nstatic.p; A.rows = c->d_rows.p;
     A.row_flags = c->d_flags.p; A.row_id = c->d_id.p; A.row_cell = c->d_row_cell.p; A.row_aabb = c->d_aabb.p;
     A.nsh = c->nsh; A.sh_keys = c->d_sh_keys.p; A.sh_nk = c->d_sh_nk.p; A.sh_begin = c->d_sh_begin.p; A.sh_nact = c->d_sh_nact.p; A.sh_nstat = c->d_sh_nstat.p;
-    const uint32_t seq = ++c->boxq_calls;
-    A.hdr = c->d_boxq_hdr.p; A.out = c->d_boxq_out.p; A.h_pub = c->d_hboxq_pub; A.seq = seq;
+    A.hdr = c->boxq.hdr.p; A.out = c->d_boxq_out.p; A.h_pub = c->boxq.d_pub; A.seq = c->boxq.next_seq();
     const uint32_t grid = n + A.n_sh_chunks * ((n + BOXQ_TILE - 1u) / BOXQ_TILE);
     hipLaunchKernelGGL(k_box_query, dim3(grid), dim3(BOXQ_THREADS), 0, st, A);
     HIPCHK(c, hipGetLastError());
     uint32_t nrec = 0;
-    {   // completion: the sequence number the last workgroup publishes in mapped host memory (as re_logic_list waits)
-        auto sync = [&]() -> int { HIPCHK(c, sync_stream(st)); std::atomic_thread_fence(std::memory_order_acquire); return RE_OK; };
-        int rc = poll_word(&c->h_boxq_pub->seq, seq, std::chrono::milliseconds(5)) ? RE_OK : sync();
-        if (rc != RE_OK) return rc;
-        auto sealed = [&]() { const volatile LogicPublished *q = c->h_boxq_pub; return q->seal == logic_seal(q->n, seq); };
-        settle_seal(sealed, std::chrono::microseconds(500), c->n_seal_waits, c->n_sync_fallbacks, [&] { rc = sync(); });   // (counted, asserted to be 0 by the tests)
-        if (rc != RE_OK) return rc;
-        nrec = c->h_boxq_pub->n;
-    }
+    { int rc = c->boxq.wait(c, A.seq, &nrec); if (rc != RE_OK) return rc; }
     const uint32_t nw = std::min(nrec, cap_dev);
     if (nw) HIPCHK(c, hipMemcpy(hits, c->d_boxq_out.p, (size_t)nw * sizeof(re_box_hit), hipMemcpyDeviceToHost));
     if (n_total) *n_total = nrec;

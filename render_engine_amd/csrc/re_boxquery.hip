@@ -218,8 +218,7 @@ __device__ __forceinline__ void boxq_shared_part(const BoxQueryArgs &A, BoxqShar
 // Grid: workgroups [0, n) take one query each through the unique sections; the workgroups behind them take (256 shared sections) x (256 queries) each.
 // 256 threads, 64-wide waves, no recursion; every loop is bounded (candidate cells by the host's cap, rb_find's probe by an empty slot of an overlay that is
 // never full and a binary search, the row walks by the sections' counts).
-// Publication is k_logic_list's: write-through records, every wave waits for its own stores, the workgroups sign off on 32 shard counters and one
-// on top, and the last one publishes count, seal and sequence number into mapped host memory and leaves the header zero for the next call.
+// Publication: write-through records, every wave waits for its own stores, then the workgroup signs off (list_sign_off, re_kernels.h).
 __global__ __launch_bounds__(BOXQ_THREADS) void k_box_query(BoxQueryArgs A) {
     __shared__ BoxqShared S;
     if (threadIdx.x == 0) { S.n_hits = 0u; S.n_queue = 0u; }
@@ -227,18 +226,7 @@ __global__ __launch_bounds__(BOXQ_THREADS) void k_box_query(BoxQueryArgs A) {
     if (blockIdx.x < A.n) boxq_unique_part(A, S); else boxq_shared_part(A, S);
     wait_own_stores();
     __syncthreads();                                                          // every wave's records have left; the count atomics have returned
-    if (threadIdx.x != 0) return;
-    const uint32_t sh = blockIdx.x & (LOGIC_TICKET_SHARDS - 1u);
-    const uint32_t expect = (gridDim.x - sh + LOGIC_TICKET_SHARDS - 1u) / LOGIC_TICKET_SHARDS;     // workgroups whose index is sh modulo 32
-    if (atomicAdd(&A.hdr->shard[sh * LOGIC_LINE_WORDS], 1u) + 1u != expect) return;
-    const uint32_t ntop = gridDim.x < LOGIC_TICKET_SHARDS ? gridDim.x : LOGIC_TICKET_SHARDS;
-    if (atomicAdd(&A.hdr->top, 1u) + 1u != ntop) return;
-    // the last workgroup of the launch: every count atomic has been performed (agent scope: at the device's coherence point)
-    const uint32_t total = atomicExch(&A.hdr->count, 0u);
-    atomicExch(&A.hdr->top, 0u);                                              // the block is all zero again for the next call (stream order)
-    for (uint32_t k = 0; k < ntop; k++) atomicExch(&A.hdr->shard[k * LOGIC_LINE_WORDS], 0u);
-    A.h_pub->n = total; A.h_pub->seal = logic_seal(total, A.seq);
-    publish_to_host(&A.h_pub->seq, A.seq);
+    if (threadIdx.x == 0) list_sign_off(A.hdr, A.h_pub, A.seq);
 }
 
 }  // namespace re

@@ -296,6 +296,26 @@ struct LogicHeader {                       // device block of k_logic_list; all 
 };
 struct LogicPublished { uint32_t n, seal, seq, pad; };                  // mapped host memory: the record count, its seal, and the call's sequence number (written last, publish_to_host)
 RE_HD uint32_t logic_seal(uint32_t n, uint32_t seq) { return table_word_hash(n, 1u) ^ table_word_hash(seq, 2u); }
+// Two-level sign-off of `total` participants (nobody waits for anybody): a shard counter is complete at signoff_expect (participants with index `shard` modulo nshards), the one on top at signoff_top (shards with any).
+RE_HD uint32_t signoff_expect(uint32_t total, uint32_t shard, uint32_t nshards) { return (total - shard + nshards - 1u) / nshards; }
+RE_HD uint32_t signoff_top(uint32_t total, uint32_t nshards) { return total < nshards ? total : nshards; }
+#if defined(__HIPCC__)
+// The end of a kernel that answers with a list of records and a count (k_logic_list, k_box_query): thread 0 of every workgroup, after wait_own_stores() in every wave and a barrier.
+// The workgroup that completes the sign-off publishes count, seal and sequence number into mapped host memory and leaves the header all zero; the host side is ListChannel (re_api.hip).
+__device__ __forceinline__ void list_sign_off(LogicHeader *hdr, LogicPublished *h_pub, uint32_t seq) {
+    const uint32_t sh = blockIdx.x & (LOGIC_TICKET_SHARDS - 1u);
+    const uint32_t expect = signoff_expect(gridDim.x, sh, LOGIC_TICKET_SHARDS);     // workgroups whose index is sh modulo 32
+    if (atomicAdd(&hdr->shard[sh * LOGIC_LINE_WORDS], 1u) + 1u != expect) return;
+    const uint32_t ntop = signoff_top(gridDim.x, LOGIC_TICKET_SHARDS);
+    if (atomicAdd(&hdr->top, 1u) + 1u != ntop) return;
+    // the last workgroup of the launch: every count atomic has been performed (agent scope: at the device's coherence point)
+    const uint32_t total = atomicExch(&hdr->count, 0u);
+    atomicExch(&hdr->top, 0u);                                                // the block is all zero again for the next call (stream order)
+    for (uint32_t k = 0; k < ntop; k++) atomicExch(&hdr->shard[k * LOGIC_LINE_WORDS], 0u);
+    h_pub->n = total; h_pub->seal = logic_seal(total, seq);
+    publish_to_host(&h_pub->seq, seq);
+}
+#endif
 RE_HD uint32_t tick_seal(uint32_t n_changed, uint32_t n_rebucket, uint32_t n_oob, uint32_t seq) {   // TickHeader::pad[0] of the host copy (tick_sign_off, k_apply_small)
     return table_word_hash(n_changed, 1u) ^ table_word_hash(n_rebucket, 2u) ^ table_word_hash(n_oob, 3u) ^ table_word_hash(seq, 4u);
 }

@@ -1337,7 +1337,7 @@ __device__ __forceinline__ void sync_frame_publish(FrameHeader *hdr, const ItemS
         publish_to_host(&A.hres->done_frame, A.frame);
     }
 }
-// the tail of a publishing scan launch, after scan_cull_body: every workgroup signs off on the sharded ticket, the last one publishes the frame
+// the tail of a publishing scan launch, after scan_cull_body: every workgroup signs off on the sharded ticket, the last one publishes the frame (counts: signoff_expect / signoff_top, re_kernels.h)
 __device__ __forceinline__ void sync_sign_off() {
     wait_own_stores();                                        // this wave's list entries (write-through) and atomics have been performed ...
     __syncthreads();                                          // ... before the workgroup signs off
@@ -1622,7 +1622,7 @@ __device__ __forceinline__ void tick_sign_off(TickHeader *th, TickHeader *h_th, 
     // out-of-bounds lists are plain stores; their reader is the host behind the end of the kernel.)
     wait_own_stores();
     const uint32_t wpb = blockDim.x >> 6, W = gridDim.x * wpb, wv = blockIdx.x * wpb + (threadIdx.x >> 6), sh = wv & (TICK_TICKET_SHARDS - 1u);
-    const uint32_t expect = (W - sh + TICK_TICKET_SHARDS - 1u) / TICK_TICKET_SHARDS;          // waves whose index is sh modulo 32
+    const uint32_t expect = (W - sh + TICK_TICKET_SHARDS - 1u) / TICK_TICKET_SHARDS;          // waves whose index is sh modulo 32 (signoff_expect / signoff_top, re_kernels.h)
     if (atomicAdd(&th->shard[sh * TICK_SHARD_STRIDE + 1u], 1u) + 1u != expect) return;
     const uint32_t ntop = W < TICK_TICKET_SHARDS ? W : TICK_TICKET_SHARDS;
     if (atomicAdd(&th->pad[1], 1u) + 1u != ntop) return;                    // (issued after the atomic above has returned)

@@ -22,8 +22,7 @@ __device__ __forceinline__ uint32_t logic_mbcnt(uint64_t mask) {
 // Compaction: ballot + mbcnt inside the wave, the four waves' counts summed in LDS, ONE global atomicAdd per workgroup that lists anything.  Each listed row
 // yields at most one record, so a list of n records cannot overflow.
 // The records are read by the host as soon as it has seen the count -- while other workgroups' plain stores could still sit in their XCD's L2 --, so they
-// are write-through stores (sc1), every storing wave waits for its own (s_waitcnt vmcnt(0)) before its workgroup signs off, and the workgroup that completes
-// the sign-off (32 shard counters, then one on top: nobody waits for anybody) publishes count, seal and sequence number into mapped host memory.
+// are write-through stores (sc1), and every storing wave waits for its own (s_waitcnt vmcnt(0)) before its workgroup signs off (list_sign_off, re_kernels.h).
 __global__ __launch_bounds__(256) void k_logic_list(uint32_t n, const uint32_t *__restrict__ rows, const uint32_t *__restrict__ words, const uint32_t *__restrict__ row_flags,
                                                     const uint32_t *__restrict__ row_id, const uint32_t *__restrict__ row_cell, const uint32_t *__restrict__ cell_stamp,
                                                     const uint8_t *__restrict__ cell_flags, const int32_t *__restrict__ sh_cells, const Aabb *__restrict__ sh_aabb,
@@ -56,18 +55,7 @@ __global__ __launch_bounds__(256) void k_logic_list(uint32_t n, const uint32_t *
     }
     if (listed) wait_own_stores();
     __syncthreads();                                                          // every wave's records have left; the count atomic has returned
-    if (threadIdx.x != 0) return;
-    const uint32_t sh = blockIdx.x & (LOGIC_TICKET_SHARDS - 1u);
-    const uint32_t expect = (gridDim.x - sh + LOGIC_TICKET_SHARDS - 1u) / LOGIC_TICKET_SHARDS;     // workgroups whose index is sh modulo 32
-    if (atomicAdd(&hdr->shard[sh * LOGIC_LINE_WORDS], 1u) + 1u != expect) return;
-    const uint32_t ntop = gridDim.x < LOGIC_TICKET_SHARDS ? gridDim.x : LOGIC_TICKET_SHARDS;
-    if (atomicAdd(&hdr->top, 1u) + 1u != ntop) return;
-    // the last workgroup of the launch: every count atomic has been performed (agent scope: at the device's coherence point)
-    const uint32_t total = atomicExch(&hdr->count, 0u);
-    atomicExch(&hdr->top, 0u);                                                // the block is all zero again for the next call (stream order)
-    for (uint32_t k = 0; k < ntop; k++) atomicExch(&hdr->shard[k * LOGIC_LINE_WORDS], 0u);
-    h_pub->n = total; h_pub->seal = logic_seal(total, seq);
-    publish_to_host(&h_pub->seq, seq);
+    if (threadIdx.x == 0) list_sign_off(hdr, h_pub, seq);
 }
 
 }  // namespace re

@@ -35,4 +35,22 @@ inline Seal settle_seal(Sealed &&sealed, std::chrono::steady_clock::duration lim
     return sealed() ? Seal::after_sync : Seal::never;
 }
 
+// "Poll, else synchronise and fence", for a word with no seal behind it.  `sync` is the caller's synchronise, 0 when it succeeded; returns 0, or what `sync` returned.
+template <typename Sync>
+inline int wait_word(const volatile uint32_t *word, uint32_t want, std::chrono::steady_clock::duration poll_limit, Sync &&sync) {
+    if (poll_word(word, want, poll_limit)) return 0;
+    if (const int rc = sync()) return rc;
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return 0;
+}
+
+// The whole wait for a sealed block: the word, then the seal.  A failed synchronise ends it at once -- no look at the seal, no counter touched.
+// After a synchronise that succeeded the stream's end is authoritative: the caller reads the block whatever the seal says.
+template <typename Sealed, typename Sync>
+inline int wait_sealed(const volatile uint32_t *word, uint32_t want, std::chrono::steady_clock::duration poll_limit, Sealed &&sealed, std::chrono::steady_clock::duration seal_limit, uint32_t &n_seal_waits, uint32_t &n_sync_fallbacks, Sync &&sync) {
+    int rc = wait_word(word, want, poll_limit, sync);
+    if (rc == 0) settle_seal(sealed, seal_limit, n_seal_waits, n_sync_fallbacks, [&] { rc = sync(); });
+    return rc;
+}
+
 }  // namespace re

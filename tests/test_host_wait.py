@@ -1,5 +1,6 @@
-"""The host half of the publication protocol (csrc/re_wait.h: poll_word, settle_seal) and the seals the kernels share with the host
-(csrc/re_kernels.h: tick_seal, col_seal), as a stand-alone g++ program: no device, no library.  The cases are in tests/cpp/wait_test.cpp."""
+"""The host half of the publication protocol (csrc/re_wait.h: poll_word, settle_seal, wait_word, wait_sealed) and the seals and sign-off counts
+the kernels share with the host (csrc/re_kernels.h: tick_seal, col_seal, logic_seal, signoff_expect, signoff_top), as a stand-alone g++ program:
+no device, no library.  The cases are in tests/cpp/wait_test.cpp."""
 import os
 import subprocess
 
