@@ -395,6 +395,30 @@ typedef struct { uint32_t need_flags, forbid_flags, reserved[2]; } re_box_query_
 int re_query_boxes(re_ctx *ctx, const float *boxes6 /* [n * 6]: xmin xmax ymin ymax zmin zmax */, uint32_t n,
                    const re_box_query_args *args, re_box_hit *hits, uint32_t capacity, uint32_t *n_total);
 
+/* The other question game logic asks of a spatial index: what lies along this line -- a shot, a line of sight, a pick ray.  For a whole batch of segments
+ * at once: every record (query index, entity id, t_enter, t_exit) such that
+ *   the entity is one re_query_boxes would consider (live, in the tree, no RE_F_PHANTOM replica, no ghost instance; args filters as there), is not the
+ *   segment's exclude_entity (RE_SEGMENT_NO_ENTITY: none; a shooter excludes itself), and
+ *   the segment p0 + t * d, t in [0, 1], d = p1 - p0 (one f32 subtraction per axis; a subnormal component counts as 0), meets its stored StaticAABB
+ *   (RE_C_STATIC_AABB, unclipped) by the slab test, in plain f32 with IEEE division, in this order:
+ *       lo = 0, hi = 1
+ *       for a in x, y, z:   (mn, mx = the box's bounds on a)
+ *           if d[a] == 0:  if !(p0[a] >= mn && p0[a] <= mx) -> miss
+ *           else:          u = (mn - p0[a]) / d[a];  v = (mx - p0[a]) / d[a];  if u > v swap
+ *                          if u > lo: lo = u;   if v < hi: hi = v
+ *       hit iff lo <= hi;   t_enter = lo, t_exit = hi
+ *   Intervals are closed: a segment that only touches a face, an edge or a corner hits.  p0 == p1 is a point query; a p0 inside the box gives t_enter = 0.
+ * Each pair is reported once, in no particular order; the first hit of a query is the record with the smallest (t_enter, entity_id), found by the caller.
+ * *n_total, capacity, hits and the calling contract are those of re_query_boxes: synchronous, valid at any point between calls, no frame stamps read.
+ * RE_E_ARG (the message names the first offending segment, nothing is touched): a non-finite endpoint or p1 - p0, a segment whose bounding box exceeds
+ * RE_BOX_QUERY_MAX_CELLS candidate world sections (a diagonal of about 30 atomic lengths per axis passes; axis-aligned segments may be far longer),
+ * n > RE_BOX_QUERY_MAX_QUERIES, nonzero reserved words, capacity without a buffer.  RE_E_STATE before any upload.  n == 0, or a world without entities: no hits. */
+typedef struct { float p0[3], p1[3]; uint32_t exclude_entity /* RE_SEGMENT_NO_ENTITY: none */, reserved /* 0 */; } re_segment;   /* 32 bytes */
+typedef struct { uint32_t query, entity_id; float t_enter, t_exit; } re_segment_hit;                                             /* 16 bytes */
+#define RE_SEGMENT_NO_ENTITY 0xFFFFFFFFu
+int re_query_segments(re_ctx *ctx, const re_segment *segments, uint32_t n, const re_box_query_args *args,
+                      re_segment_hit *hits, uint32_t capacity, uint32_t *n_total);
+
 /* ECS read-back for user logic (LogicFunction reads components through &ECS, exports/logic_components.rs:15-18).  A component the entity does not
  * carry (never written, or removed by RE_CHANGE_REMOVE_COMPONENT) yields RE_E_ARG == ECS::get_copy -> None (objects/ecs.rs:653-664). */
 int re_read_component(re_ctx *ctx, uint32_t entity_id, int component, void *dst);

@@ -401,6 +401,31 @@ class Pipeline {
         hits.resize(std::min<size_t>(hits.size(), n));
         return hits;
     }
+    // ... and what lies along a line -- a shot, a line of sight, a pick ray: the entities whose StaticAABB each segment meets, as (index of the segment, entity,
+    // t_enter, t_exit) records in no particular order, each pair once; the segment is p0 + t * (p1 - p0), t in [0, 1].  exclude_entity of a segment is not
+    // reported (a shooter excludes itself; RE_SEGMENT_NO_ENTITY: none).  first_hits picks the nearest of each segment.
+    struct Segment { TVec3 p0, p1; EntityId exclude_entity = RE_SEGMENT_NO_ENTITY; };
+    std::vector<re_segment_hit> find_entities_along_segments(const std::vector<Segment> &segments, uint32_t need_flags = 0u, uint32_t forbid_flags = 0u) {
+        upload_if_needed();
+        std::vector<re_segment> s; s.reserve(segments.size());
+        for (const Segment &g : segments) s.push_back(re_segment{ { g.p0.x, g.p0.y, g.p0.z }, { g.p1.x, g.p1.y, g.p1.z }, g.exclude_entity, 0u });
+        const re_box_query_args args{ need_flags, forbid_flags, { 0u, 0u } };
+        uint32_t n = 0; check(re_query_segments(ctx_, s.data(), (uint32_t)s.size(), &args, nullptr, 0u, &n), "re_query_segments");
+        std::vector<re_segment_hit> hits(n);
+        if (n) check(re_query_segments(ctx_, s.data(), (uint32_t)s.size(), &args, hits.data(), n, &n), "re_query_segments");
+        hits.resize(std::min<size_t>(hits.size(), n));
+        return hits;
+    }
+    // per segment 0 .. n - 1 the record with the smallest (t_enter, entity_id), or nothing: the first thing the segment meets.  The ordering is the host's.
+    static std::vector<std::optional<re_segment_hit>> first_hits(const std::vector<re_segment_hit> &hits, size_t n) {
+        std::vector<std::optional<re_segment_hit>> first(n);
+        for (const re_segment_hit &h : hits) {
+            if (h.query >= n) continue;
+            std::optional<re_segment_hit> &f = first[h.query];
+            if (!f || h.t_enter < f->t_enter || (h.t_enter == f->t_enter && h.entity_id < f->entity_id)) f = h;
+        }
+        return first;
+    }
     bool has_component(EntityId e, uint32_t ecs_bit) { upload_if_needed(); uint32_t bits = 0; check(re_ecs_bitset(ctx_, e, &bits), "re_ecs_bitset"); return (bits >> ecs_bit) & 1u; }   // ecs_bit: RE_ECS_BIT_*
     re_ctx *context() { upload_if_needed(); return ctx_; }
 

@@ -26,6 +26,9 @@ pub const RE_LOGIC_ENTITY: u32 = 1; pub const RE_LOGIC_RANDOM: u32 = 2;
 #[repr(C)] #[derive(Copy, Clone)] pub struct ReBoxHit { pub query: u32, pub entity_id: u32 }                                                    // 8 bytes
 #[repr(C)] #[derive(Copy, Clone, Default)] pub struct ReBoxQueryArgs { pub need_flags: u32, pub forbid_flags: u32, pub reserved: [u32; 2] }      // null: no filter; reserved must be 0
 pub const RE_BOX_QUERY_MAX_CELLS: u32 = 32768; pub const RE_BOX_QUERY_MAX_QUERIES: u32 = 1 << 20;
+#[repr(C)] #[derive(Copy, Clone)] pub struct ReSegment { pub p0: [f32; 3], pub p1: [f32; 3], pub exclude_entity: u32, pub reserved: u32 }          // 32 bytes; exclude_entity: RE_SEGMENT_NO_ENTITY for none; reserved must be 0
+#[repr(C)] #[derive(Copy, Clone)] pub struct ReSegmentHit { pub query: u32, pub entity_id: u32, pub t_enter: f32, pub t_exit: f32 }             // 16 bytes
+pub const RE_SEGMENT_NO_ENTITY: u32 = 0xFFFF_FFFF;
 #[repr(C)] pub struct ReGathered { pub n_ranks: u32, pub overflowed: u32, pub counts: *const u32, pub d_entity_ids: *const u32, pub ids_rank_stride: u32,
                                    pub d_matrices: *const f32, pub matrices_rank_stride: u32 }
 #[repr(C)] #[derive(Copy, Clone, Default)] pub struct ReEntityState { pub entity_id: u32, pub model_index: u32, pub render_system: u32, pub sortable: u32, pub flags: u32,
@@ -70,6 +73,7 @@ extern "C" {
     pub fn re_set_entity_logic(ctx: *mut ReCtx, table: *const ReEntityLogic, n: u32) -> c_int;                 // replaces the table
     pub fn re_logic_list(ctx: *mut ReCtx, flags: u32, calls: *mut ReLogicCall, capacity: u32, n_total: *mut u32) -> c_int;
     pub fn re_query_boxes(ctx: *mut ReCtx, boxes6: *const f32 /* [n * 6]: xmin xmax ymin ymax zmin zmax */, n: u32, args: *const ReBoxQueryArgs, hits: *mut ReBoxHit, capacity: u32, n_total: *mut u32) -> c_int;
+    pub fn re_query_segments(ctx: *mut ReCtx, segments: *const ReSegment, n: u32, args: *const ReBoxQueryArgs, hits: *mut ReSegmentHit, capacity: u32, n_total: *mut u32) -> c_int;
     pub fn re_wait(ctx: *mut ReCtx, vis: *mut ReVisible, tick: *mut ReTickResult) -> c_int;
     pub fn re_copy_visible(ctx: *mut ReCtx, ids: *mut u32, mats: *mut f32, capacity: u32, n_written: *mut u32) -> c_int;
     pub fn re_set_output_buffers(ctx: *mut ReCtx, d_ids: *mut u32, d_mats: *mut f32, capacity: u32) -> c_int;

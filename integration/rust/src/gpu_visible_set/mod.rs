@@ -10,7 +10,7 @@ use std::ffi::CStr;
 use std::mem::MaybeUninit;
 
 /// One resident copy of the world on one GPU.
-pub struct GpuVisibleSet { ctx: *mut ReCtx, collision_pairs: Vec<ReCollision>, logic_list: Vec<ReLogicCall>, box_hits: Vec<ReBoxHit> }
+pub struct GpuVisibleSet { ctx: *mut ReCtx, collision_pairs: Vec<ReCollision>, logic_list: Vec<ReLogicCall>, box_hits: Vec<ReBoxHit>, segment_hits: Vec<ReSegmentHit> }
 
 // the context is driven from the render thread only (Pipeline::execute), like the flows it replaces
 unsafe impl Send for GpuVisibleSet {}
@@ -51,7 +51,7 @@ impl GpuVisibleSet {
         let mut ctx: *mut ReCtx = std::ptr::null_mut();
         let rc = unsafe { re_create(&cfg, &mut ctx) };
         if rc != RE_OK { return Err(GpuError { code: rc, message: last_error(std::ptr::null()) }); }
-        Ok(GpuVisibleSet { ctx, collision_pairs: Vec::with_capacity(4096), logic_list: Vec::with_capacity(4096), box_hits: Vec::with_capacity(4096) })
+        Ok(GpuVisibleSet { ctx, collision_pairs: Vec::with_capacity(4096), logic_list: Vec::with_capacity(4096), box_hits: Vec::with_capacity(4096), segment_hits: Vec::with_capacity(4096) })
     }
 
     fn check(&self, rc: i32) -> Result<(), GpuError> {
@@ -316,6 +316,33 @@ impl GpuVisibleSet {
             if n <= cap { unsafe { self.box_hits.set_len(n as usize) }; return Ok(&self.box_hits); }
             self.box_hits = Vec::with_capacity(n as usize + n as usize / 4);            // more pairs than the buffer holds: once more with room
         }
+    }
+
+    /// What lies along a line -- a shot, a line of sight, a pick ray: the entities whose StaticAABB each segment of a batch meets, as
+    /// (query index, entity id, t_enter, t_exit) records in no particular order, each pair once; the segment is p0 + t * (p1 - p0), t in [0, 1].
+    /// A shooter excludes itself with `exclude_entity` (`RE_SEGMENT_NO_ENTITY`: nobody); `filter` as `entities_in_boxes`.  Valid at any point between calls.
+    pub fn entities_along_segments(&mut self, segments: &[ReSegment], filter: Option<&ReBoxQueryArgs>) -> Result<&[ReSegmentHit], GpuError> {
+        let args = filter.map_or(std::ptr::null(), |f| f as *const ReBoxQueryArgs);
+        loop {
+            let mut n = 0u32;
+            let cap = self.segment_hits.capacity() as u32;
+            let rc = unsafe { ffi::re_query_segments(self.ctx, segments.as_ptr(), segments.len() as u32, args, self.segment_hits.as_mut_ptr(), cap, &mut n) };
+            self.check(rc)?;
+            if n <= cap { unsafe { self.segment_hits.set_len(n as usize) }; return Ok(&self.segment_hits); }
+            self.segment_hits = Vec::with_capacity(n as usize + n as usize / 4);        // more records than the buffer holds: once more with room
+        }
+    }
+
+    /// The first thing each of `n` segments meets: per query index the record with the smallest (t_enter, entity_id), or None.  The ordering is the
+    /// host's; the device reports every hit.
+    pub fn first_hits(hits: &[ReSegmentHit], n: usize) -> Vec<Option<ReSegmentHit>> {
+        let mut first: Vec<Option<ReSegmentHit>> = vec![None; n];
+        for h in hits {
+            let Some(slot) = first.get_mut(h.query as usize) else { continue };
+            let nearer = match slot { None => true, Some(f) => h.t_enter < f.t_enter || (h.t_enter == f.t_enter && h.entity_id < f.entity_id) };
+            if nearer { *slot = Some(*h); }
+        }
+        first
     }
 
     /// flows/logic_flow.rs:230 + the kinematic part of :255 (update_positions, apply_change of the kinematic requests).

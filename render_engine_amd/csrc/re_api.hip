@@ -11,6 +11,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <string>
 #include <thread>
@@ -274,6 +275,8 @@ struct re_ctx {
     DevBuf<uint32_t> d_logic_rows, d_logic_words; DevBuf<unsigned long long> d_logic_out; ListChannel logic; uint32_t logic_n = 0; bool logic_dirty = true;
     // tree queries (re_query_boxes): the batch travels from two pinned buffers that alternate by call into one device array; records come back through d_boxq_out
     BoxQuery *h_boxq[2] = {}; size_t h_boxq_cap[2] = {}; uint32_t boxq_k = 0; DevBuf<BoxQuery> d_boxq; DevBuf<unsigned long long> d_boxq_out; ListChannel boxq;
+    // ... and re_query_segments: the same arrangement with buffers, header block, mapped block and sequence numbers of its own
+    SegQuery *h_segq[2] = {}; size_t h_segq_cap[2] = {}; uint32_t segq_k = 0; DevBuf<SegQuery> d_segq; DevBuf<unsigned long long> d_segq_out; ListChannel segq;
 };
 
 #define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return (ctx)->fail(RE_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
@@ -379,6 +382,8 @@ static void release_flows(re_ctx *c) {
     if (c->h_col) { (void)hipHostFree(c->h_col); c->h_col = c->d_hcol = nullptr; }
     c->logic.close(); c->boxq.close(); c->d_boxq.release(nullptr); c->d_boxq_out.release(nullptr);
     for (int k = 0; k < 2; k++) if (c->h_boxq[k]) { (void)hipHostFree(c->h_boxq[k]); c->h_boxq[k] = nullptr; c->h_boxq_cap[k] = 0; }
+    c->segq.close(); c->d_segq.release(nullptr); c->d_segq_out.release(nullptr);
+    for (int k = 0; k < 2; k++) if (c->h_segq[k]) { (void)hipHostFree(c->h_segq[k]); c->h_segq[k] = nullptr; c->h_segq_cap[k] = 0; }
 }
 static void free_world(re_ctx *c) {
     uint64_t *a = &c->dev_bytes;
@@ -4194,3 +4199,77 @@ extern "C" int re_query_boxes(re_ctx *c, const float *boxes6, uint32_t n, const 
     if (n_total) *n_total = nrec;
     return RE_OK;
 } RE_ABI_GUARD(c, "re_query_boxes")
+
+// ... and the entities along a batch of segments (k_segment_query, re_segquery.hip): the same contract, the same record-list protocol on a channel of its own
+static_assert(sizeof(re_segment) == 32 && sizeof(re_segment_hit) == 16 && sizeof(SegQuery) == 64, "record layouts of include/re_hip.h / re_kernels.h");
+extern "C" int re_query_segments(re_ctx *c, const re_segment *segments, uint32_t n, const re_box_query_args *args, re_segment_hit *hits, uint32_t capacity, uint32_t *n_total) try {
+    if (!c) return RE_E_ARG;
+    if (n > RE_BOX_QUERY_MAX_QUERIES) return c->fail(RE_E_ARG, "re_query_segments: %u segments (at most %u a call)", n, RE_BOX_QUERY_MAX_QUERIES);
+    if (n && !segments) return c->fail(RE_E_ARG, "re_query_segments: segments is NULL");
+    if (capacity && !hits) return c->fail(RE_E_ARG, "re_query_segments: capacity without a buffer");
+    if (args && (args->reserved[0] || args->reserved[1])) return c->fail(RE_E_ARG, "re_query_segments: reserved must be 0");
+    if (!c->h_res) return c->fail(RE_E_STATE, "re_query_segments: no world uploaded");
+    if (c->cfg.outline_length > (1u << 30)) return c->fail(RE_E_UNSUPPORTED, "re_query_segments: outline lengths beyond 2^30 are not supported (32-bit cell arithmetic)");
+    if (n_total) *n_total = 0;
+    if (n == 0) return RE_OK;
+    // the batch, checked whole before anything is touched: built in the pinned buffer that was not the last call's source
+    const uint32_t k = c->segq_k ^= 1u;
+    if (c->h_segq_cap[k] < n) {
+        if (c->h_segq[k]) { (void)hipHostFree(c->h_segq[k]); c->h_segq[k] = nullptr; c->h_segq_cap[k] = 0; }
+        const size_t cap = std::max<size_t>((size_t)n + n / 2, 256);
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_segq[k]), cap * sizeof(SegQuery), hipHostMallocDefault));
+        c->h_segq_cap[k] = cap;
+    }
+    SegQuery *hq = c->h_segq[k];
+    const float margin = segment_query_margin(c->cfg.outline_length);
+    for (uint32_t i = 0; i < n; i++) {
+        const re_segment &s = segments[i];
+        if (s.reserved) return c->fail(RE_E_ARG, "re_query_segments: segment %u: reserved must be 0", i);
+        SegQuery &q = hq[i];
+        float bb[6];
+        for (int a = 0; a < 3; a++) {
+            float d = s.p1[a] - s.p0[a];
+            if (!std::isfinite(s.p0[a]) || !std::isfinite(s.p1[a]) || !std::isfinite(d)) return c->fail(RE_E_ARG, "re_query_segments: segment %u is not finite (an endpoint, or p1 - p0)", i);
+            if (std::fabs(d) < std::numeric_limits<float>::min()) d = 0.0f;                             // (the kernel never divides by a subnormal)
+            q.p0[a] = s.p0[a]; q.d[a] = d;
+            bb[2 * a] = std::min(s.p0[a], s.p1[a]) - margin; bb[2 * a + 1] = std::max(s.p0[a], s.p1[a]) + margin;
+        }
+        // the candidate cells are those of the bounding box, inflated by the margin: the slab test accepts t = 1 after rounding for a face a few ulps beyond p1
+        BoxQuery b;
+        const uint64_t cells = make_box_query(bb, c->cfg.outline_length, c->cfg.atomic_length, c->maxlevel, &b);
+        if (cells > RE_BOX_QUERY_MAX_CELLS) return c->fail(RE_E_ARG, "re_query_segments: the bounding box of segment %u covers %llu candidate cells (at most %u: about 30 atomic lengths per axis for a diagonal)", i, (unsigned long long)cells, RE_BOX_QUERY_MAX_CELLS);
+        q.exclude = s.exclude_entity; q.flags = b.flags; q.ncells = b.ncells; q.pad = 0;
+        for (int a = 0; a < 3; a++) { q.umin[a] = b.umin[a]; q.umax[a] = b.umax[a]; }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = settle_frame(c); if (rc != RE_OK) return rc; }                  // (an asynchronous cull or tick in flight is finished first; the query reads no frame stamps)
+    if (!c->n || !c->ncells) return RE_OK;                                     // a world without rows
+    { int rc = ensure_device_lookup(c, true); if (rc != RE_OK) return rc; }
+    hipStream_t st = c->stream;
+    { int rc = c->segq.open(c); if (rc != RE_OK) return rc; }
+    const uint32_t cap_dev = (uint32_t)std::min<uint64_t>(capacity, (uint64_t)n * c->n);      // (no more pairs than segments x rows exist)
+    if (c->d_segq.n < n || !c->d_segq.p || c->d_segq_out.n < (size_t)cap_dev * 2u || !c->d_segq_out.p) {      // a buffer that must grow is replaced only after the stream has drained
+        HIPCHK(c, sync_stream(st));
+        if (c->d_segq.n < n || !c->d_segq.p) HIPCHK(c, c->d_segq.alloc((size_t)n + n / 2, nullptr));
+        if (c->d_segq_out.n < (size_t)cap_dev * 2u || !c->d_segq_out.p) HIPCHK(c, c->d_segq_out.alloc(((size_t)cap_dev + cap_dev / 2) * 2u, nullptr));
+    }
+    HIPCHK(c, hipMemcpyAsync(c->d_segq.p, hq, (size_t)n * sizeof(SegQuery), hipMemcpyHostToDevice, st));
+    SegQueryArgs A{};
+    A.n = n; A.n_sh_chunks = c->nsh ? (c->nsh + BOXQ_THREADS - 1u) / BOXQ_THREADS : 0u;
+    A.atomic = c->cfg.atomic_length; A.max_level = c->maxlevel; A.need = args ? args->need_flags : 0u; A.forbid = args ? args->forbid_flags : 0u; A.nrows = c->n; A.capacity = cap_dev;
+    A.outline = c->cfg.outline_length; A.margin = margin;
+    A.q = c->d_segq.p; A.T = rb_tables(c); A.cell_key = c->d_cell_key.p; A.cell_begin = c->d_cell_begin.p; A.cell_nl = c->d_cell_nlocal.p; A.cell_ns = c->d_cell_nstatic.p; A.rows = c->d_rows.p;
+    A.row_flags = c->d_flags.p; A.row_id = c->d_id.p; A.row_cell = c->d_row_cell.p; A.row_aabb = c->d_aabb.p;
+    A.nsh = c->nsh; A.sh_keys = c->d_sh_keys.p; A.sh_nk = c->d_sh_nk.p; A.sh_begin = c->d_sh_begin.p; A.sh_nact = c->d_sh_nact.p; A.sh_nstat = c->d_sh_nstat.p;
+    A.hdr = c->segq.hdr.p; A.out = c->d_segq_out.p; A.h_pub = c->segq.d_pub; A.seq = c->segq.next_seq();
+    const uint32_t grid = n + A.n_sh_chunks * ((n + BOXQ_TILE - 1u) / BOXQ_TILE);
+    hipLaunchKernelGGL(k_segment_query, dim3(grid), dim3(BOXQ_THREADS), 0, st, A);
+    HIPCHK(c, hipGetLastError());
+    uint32_t nrec = 0;
+    { int rc = c->segq.wait(c, A.seq, &nrec); if (rc != RE_OK) return rc; }
+    const uint32_t nw = std::min(nrec, cap_dev);
+    if (nw) HIPCHK(c, hipMemcpy(hits, c->d_segq_out.p, (size_t)nw * sizeof(re_segment_hit), hipMemcpyDeviceToHost));
+    if (n_total) *n_total = nrec;
+    return RE_OK;
+} RE_ABI_GUARD(c, "re_query_segments")

@@ -454,6 +454,24 @@ struct BoxQueryArgs {
     LogicHeader *hdr; unsigned long long *out; LogicPublished *h_pub; uint32_t seq;      // count, sign-off and publication as k_logic_list's (a block of its own)
 };
 __global__ void k_box_query(BoxQueryArgs A);
+// tree queries for user logic (re_segquery.hip): the entities along each segment of a batch
+// One segment as the host builds it (re_query_segments): p0 and d = p1 - p0 (a subnormal component replaced by 0: the kernel never divides by one), the
+// excluded entity, and the segment's bounding box -- inflated by the margin -- as make_box_query leaves it: the candidate cells are that box's.
+struct SegQuery { float p0[3], d[3]; uint32_t exclude, umin[3], umax[3], flags, ncells, pad; };      // 64 bytes
+// The margin by which the prune inflates a cell's box (and the host the bounding box): outline * 2^-12.  The slab test's rounding error in world units is
+// bounded by about outline * 2^-21 -- three rounded operations on t <= 1 times |d| <= sqrt(3) * outline, plus the ulp of the coordinates.
+RE_HD float segment_query_margin(uint32_t outline) { return (float)outline * (1.0f / 4096.0f); }
+struct SegQueryArgs {
+    uint32_t n, n_sh_chunks;                // as BoxQueryArgs
+    uint32_t atomic, max_level, need, forbid, nrows, capacity;
+    uint32_t outline; float margin;
+    const SegQuery *q;
+    RbTables T; const uint64_t *cell_key; const uint32_t *cell_begin, *cell_nl, *cell_ns, *rows;
+    const uint32_t *row_flags, *row_id, *row_cell; const Aabb *row_aabb;
+    uint32_t nsh; const uint64_t *sh_keys; const uint8_t *sh_nk; const uint32_t *sh_begin, *sh_nact, *sh_nstat;
+    LogicHeader *hdr; unsigned long long *out; LogicPublished *h_pub; uint32_t seq;      // out: two words a record (re_segment_hit)
+};
+__global__ void k_segment_query(SegQueryArgs A);
 hipError_t sort_pairs_u64_u32(void *tmp, size_t *tmp_bytes, const uint64_t *keys_in, uint64_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out,
                               uint32_t n, unsigned begin_bit, unsigned end_bit, hipStream_t stream);      // re_sort.hip (rocPRIM radix sort)
 __global__ void k_rb_ovl_insert(uint32_t n, const Pair64 *pairs, RbTables T);

@@ -181,6 +181,22 @@ def shard_by_first_section(ents, n_shards, tree_outline_length=16384, tree_atomi
     return out
 
 
+def first_hits(hits, n):
+    """the first hit of each of the n segments of a Pipeline.find_entities_along_segments answer: (first, found) with first a SEGMENT_HIT_DT array of n
+    records -- the record with the smallest (t_enter, entity_id) of query i at index i -- and found[i] False where segment i hit nothing (first[i] is
+    then zero but for its query index).  The ordering is the host's: the device reports every hit."""
+    first = np.zeros(n, _capi.SEGMENT_HIT_DT)
+    first["query"] = np.arange(n, dtype=np.uint32)
+    found = np.zeros(n, bool)
+    if len(hits):
+        order = np.lexsort((hits["entity_id"], hits["t_enter"], hits["query"]))
+        q = hits["query"][order]
+        lead = order[np.concatenate([[True], q[1:] != q[:-1]])]
+        first[hits["query"][lead]] = hits[lead]
+        found[hits["query"][lead]] = True
+    return first, found
+
+
 class Pipeline:
     """One GPU's share of the world: BoundingBoxTree + ECS columns resident in HBM."""
 
@@ -396,6 +412,27 @@ class Pipeline:
             capacity = n.value
         hits = np.zeros(max(capacity, 1), _capi.BOX_HIT_DT)
         self._check(self._L.re_query_boxes(self._h, boxes.ctypes.data, len(boxes), args, hits.ctypes.data, capacity, C.byref(n)), "re_query_boxes")
+        return hits[:min(n.value, capacity)].copy(), n.value
+
+    def find_entities_along_segments(self, segments, exclude=None, need_flags=0, forbid_flags=0, capacity=None):
+        """the entities whose StaticAABB each segment of a batch meets ([n, 6]: p0 xyz, p1 xyz, or a SEGMENT_DT array): (hits, n_total) with hits a
+        SEGMENT_HIT_DT array (query, entity_id, t_enter, t_exit; the segment is p0 + t * (p1 - p0), t in [0, 1]) in no particular order; exclude: one
+        entity id per segment that is not reported (SEGMENT_NO_ENTITY: none), as a shooter excludes itself; the filter as find_entities_in_boxes.
+        first_hits(hits, n) picks the nearest of each segment.  Valid at any point between calls."""
+        if isinstance(segments, np.ndarray) and segments.dtype == _capi.SEGMENT_DT:
+            seg = np.ascontiguousarray(segments)
+        else:
+            pts = np.ascontiguousarray(segments, np.float32).reshape(-1, 6)
+            seg = np.zeros(len(pts), _capi.SEGMENT_DT)
+            seg["p0"], seg["p1"] = pts[:, 0:3], pts[:, 3:6]
+            seg["exclude_entity"] = _capi.SEGMENT_NO_ENTITY if exclude is None else np.asarray(exclude, np.uint32)
+        args = _capi.BoxQueryArgs(int(need_flags), int(forbid_flags)) if (need_flags or forbid_flags) else None
+        n = C.c_uint32()
+        if capacity is None:
+            self._check(self._L.re_query_segments(self._h, seg.ctypes.data, len(seg), args, None, 0, C.byref(n)), "re_query_segments")
+            capacity = n.value
+        hits = np.zeros(max(capacity, 1), _capi.SEGMENT_HIT_DT)
+        self._check(self._L.re_query_segments(self._h, seg.ctypes.data, len(seg), args, hits.ctypes.data, capacity, C.byref(n)), "re_query_segments")
         return hits[:min(n.value, capacity)].copy(), n.value
 
     # -- multi-GPU exchange (RCCL behind the C ABI) ---------------------------------------------------

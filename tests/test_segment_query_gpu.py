@@ -1,0 +1,245 @@
+"""re_query_segments on the GPU: the entities along each segment of a batch (a shot, a line of sight, a pick ray) through the C ABI against its CPU
+restatement over the oracle (tests/segment_rule.py, itself checked against the oracle's section decisions in tests/test_segment_rule.py): the pairs
+equal, t_enter and t_exit bit for bit."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import oracle as ro
+from helpers import to_oracle, oracle_camera
+from box_query_rule import probe_world, query_world
+from segment_rule import NO_ENTITY, segment_hits, records_of, first_hits_brute, draw_segments
+from test_segment_rule import known_world, known_segments
+from box_query_rule import probe_push_out
+from test_gpu_parity import build_pair, check_frame, random_changes, assert_clean_publication
+from test_logic_rule import camera_draw
+
+pytestmark = pytest.mark.gpu
+
+RE_E_ARG, RE_E_STATE = -1, -5
+F32 = np.float32
+
+
+@pytest.fixture(scope="module")
+def R():
+    import render_engine_amd as R
+    return R
+
+
+def ask(p, p0, p1, exclude=None, **k):
+    """(sorted records (query, entity, bits of t_enter, bits of t_exit), total) of one call; the pairs are distinct and as many as the total"""
+    hits, n_total = p.find_entities_along_segments(np.concatenate([p0, p1], axis=1), exclude=exclude, **k)
+    got = records_of(hits)
+    assert len(got) == n_total == len({r[:2] for r in got}), (len(got), n_total)
+    return got, n_total
+
+
+def expect_error(R, code, text, fn, *a, **k):
+    with pytest.raises(R.RenderEngineError) as e:
+        fn(*a, **k)
+    assert f"({code})" in str(e.value) and text in str(e.value), str(e.value)
+
+
+def describe(got, want):
+    return sorted(set(got) - set(want))[:6], sorted(set(want) - set(got))[:6]
+
+
+@pytest.mark.parametrize("n,seed,spread,atomic", [(2500, 5, 160.0, 64), (1500, 13, 150.0, 16)])
+def test_segment_query_parity(R, n, seed, spread, atomic):
+    """ten frames of cull, query, tick over the mixed world of test_box_query_parity with a change batch every third frame (add-entity among them):
+    64 segments a frame, every second with an excluded entity; the sorted pairs equal the rule's and t_enter / t_exit are bit-equal; frames 4 and 7 with
+    the filter, frame 5 behind an asynchronous cull and tick"""
+    L = R._capi
+    ents = query_world(n, seed, spread, atomic)
+    p, w = build_pair(R, ents, atomic=atomic)
+    ids = [int(i) for i in ents["id"]]
+    rng = np.random.default_rng(seed)
+    total = filtered = excluded = 0
+    next_id = max(ids) + 1000
+    for f in range(10):
+        cam = camera_draw(R, rng, spread)
+        oc = oracle_camera(cam)
+        if f == 5:                                                     # nothing awaited: the query finishes the frame itself (resolve)
+            assert p.cull_and_pack(cam, asynchronous=True, copy=False) is None
+            p.tick(0.05, asynchronous=True)
+            w.cull(oc); w.render(oc); w.tick(oc, 0.05)
+        else:
+            check_frame(R, p, w, cam, bool(f % 2))
+        p0, p1 = draw_segments(w, ids, rng, 16384, atomic)
+        flt = dict(need_flags=L.F_CAN_COLLIDE, forbid_flags=L.F_STATIC) if f in (4, 7) else {}
+        # every second segment excludes the nearest entity it would otherwise report
+        free = segment_hits(w, ids, p0, p1, need=flt.get("need_flags", 0), forbid=flt.get("forbid_flags", 0))
+        ex = np.full(len(p0), NO_ENTITY, np.uint32)
+        for i, r in enumerate(first_hits_brute(free, len(p0))):
+            if i % 2 and r is not None:
+                ex[i] = r[1]
+        want = segment_hits(w, ids, p0, p1, exclude=ex, need=flt.get("need_flags", 0), forbid=flt.get("forbid_flags", 0))
+        excluded += len(free) - len(want)
+        got, n_total = ask(p, p0, p1, exclude=ex, **flt)
+        assert got == want, (f, n_total, len(want), describe(got, want))
+        assert n_total == len(want), (f, n_total, len(want))
+        total += n_total; filtered += n_total if flt else 0
+        assert_clean_publication(p)
+        if f != 5:
+            n_o, oob_o = w.tick(oc, 0.05); t = p.tick(0.05)
+            assert t["n_changed"] == n_o and t["n_out_of_bounds"] == len(oob_o)
+        if f % 3 == 2:
+            ch = random_changes(R, ents, rng, 40, set())
+            add = ents[rng.integers(0, len(ents), 3)].copy()           # add-entity: three copies of existing entities under new ids, a little to the side
+            add["id"] = next_id + np.arange(3); add["pos"] += np.float32(7.5)
+            more = np.zeros(3, R.CHANGE_DT)
+            for k in range(3):
+                more[k] = (L.CHANGE_ADD_ENTITY, next_id + k, 0, k, (0, 0, 0, 0))
+            ch = np.concatenate([ch, more])
+            w.apply_changes(ch.view(ro.CHANGE_DT), added=to_oracle(add)); p.apply_changes(ch, added=add)
+            ids += [next_id + k for k in range(3)]; next_id += 3
+    assert total > 2000 and filtered > 100 and excluded > 50, (total, filtered, excluded)
+    p.close(); w.close()
+
+
+@pytest.mark.parametrize("atomic", [64, 16])
+def test_known_answers_on_the_device(R, atomic):
+    """the hand-worked segments of tests/test_segment_rule.py on both key encodings (256 sections per axis: compact 32-bit stream keys; 1024: the full
+    keys), then a static entity of the frozen cache that is moved -- reported once, at its live box, the ghost never -- and a deleted and re-created id"""
+    L = R._capi
+    s = F32(atomic) / F32(64.0)
+    ents = known_world(atomic)
+    p, w = build_pair(R, ents, atomic=atomic)
+    ids = list(range(9))
+    # change requests belong to a frame: one is drawn first (and the static render cache freezes with entity 7 in it)
+    cam = R.Camera((305.0 * s, 305.0 * s, 900.0 * s), (0, 0, -1), 3000.0)
+    check_frame(R, p, w, cam, False)
+    ch = probe_push_out()
+    w.apply_changes(ch.view(ro.CHANGE_DT)); p.apply_changes(ch)
+    p0, p1, ex, want = known_segments(atomic)
+    got, _ = ask(p, p0, p1, exclude=ex)
+    assert got == want == segment_hits(w, ids, p0, p1, exclude=ex), describe(got, want)
+    assert [r[:2] for r in ask(p, p0, p1, exclude=ex, need_flags=L.F_OOB_LOGIC)[0]] == [(8, 3)]
+    # the static entity 7 ([300, 310]^3) is moved by +500 in x: along x at y = z = 305 from 290 to 830 it is met once, at [800, 810]: 510 / 540 .. 520 / 540
+    ch = np.zeros(1, R.CHANGE_DT); ch[0] = (L.CHANGE_MODIFY, 7, L.C_POSITION, 0, (500.0 * s, 0.0, 0.0, 0.0))
+    w.apply_changes(ch.view(ro.CHANGE_DT)); p.apply_changes(ch)
+    a = np.array([[290, 305, 305], [290, 305, 305]], F32) * s; b = np.array([[320, 305, 305], [830, 305, 305]], F32) * s
+    want7 = [(1, 7, int((F32(510.0) * s / (F32(540.0) * s)).view(np.uint32)), int((F32(520.0) * s / (F32(540.0) * s)).view(np.uint32)))]
+    assert ask(p, a, b)[0] == want7 == segment_hits(w, ids, a, b)
+    assert ask(p, a, b, need_flags=L.F_STATIC)[0] == [] == segment_hits(w, ids, a, b, need=L.F_STATIC)      # (a moved entity is re-added as not static: the flag follows the tree)
+    check_frame(R, p, w, cam, False)                                                                     # the ghost is drawn ...
+    assert ask(p, a, b)[0] == want7                                                                      # ... and still not reported
+    # a deleted entity is no longer reported; its id, created again, is reported at the new place
+    a = np.array([[395, 405, 405], [395, 1405, 405]], F32) * s; b = np.array([[415, 405, 405], [415, 1405, 405]], F32) * s
+    assert ask(p, a, b)[0] == [(0, 8, F32(0.25).view(np.uint32), F32(0.75).view(np.uint32))] == segment_hits(w, ids, a, b)
+    ch = np.zeros(1, R.CHANGE_DT); ch[0] = (L.CHANGE_DELETE, 8, 0, 0, (0, 0, 0, 0))
+    w.apply_changes(ch.view(ro.CHANGE_DT)); p.apply_changes(ch)
+    assert ask(p, a, b)[0] == [] == segment_hits(w, ids, a, b)
+    add = ents[ents["id"] == 8].copy(); add["pos"][0] = (0.0, 1000.0 * s, 0.0)
+    ch = np.zeros(1, R.CHANGE_DT); ch[0] = (L.CHANGE_ADD_ENTITY, 8, 0, 0, (0, 0, 0, 0))
+    w.apply_changes(ch.view(ro.CHANGE_DT), added=to_oracle(add)); p.apply_changes(ch, added=add)
+    assert ask(p, a, b)[0] == [(1, 8, F32(0.25).view(np.uint32), F32(0.75).view(np.uint32))] == segment_hits(w, ids, a, b)
+    assert_clean_publication(p)
+    p.close(); w.close()
+
+
+def test_boundaries_of_the_call(R):
+    L = R._capi
+    lib = L.load()
+    n = C.c_uint32(77)
+    one = np.zeros(1, L.SEGMENT_DT); one["p0"] = 8100; one["p1"] = 8300; one["exclude_entity"] = NO_ENTITY
+    # before any upload
+    pe = R.Pipeline()
+    assert lib.re_query_segments(pe._h, one.ctypes.data, 1, None, None, 0, C.byref(n)) == RE_E_STATE
+    pe.close()
+    ents = query_world(600, 3, 120.0, 64)
+    p, w = build_pair(R, ents)
+    ids = [int(i) for i in ents["id"]]
+    rng = np.random.default_rng(3)
+    p0, p1 = draw_segments(w, ids, rng, 16384, 64, n=16)
+    seg = np.zeros(16, L.SEGMENT_DT); seg["p0"], seg["p1"], seg["exclude_entity"] = p0, p1, NO_ENTITY
+    both = np.concatenate([p0, p1], axis=1)
+    want = segment_hits(w, ids, p0, p1)
+    assert len(want) > 50
+    # n == 0
+    assert lib.re_query_segments(p._h, None, 0, None, None, 0, C.byref(n)) == 0 and n.value == 0
+    assert lib.re_query_segments(p._h, seg.ctypes.data, len(seg), None, None, 0, None) == 0         # n_total is optional
+    # capacity 0: the total is exact; capacity 7 of more: 7 distinct correct records, the total exact
+    hits, n_total = p.find_entities_along_segments(seg, capacity=0)
+    assert n_total == len(want) and len(hits) == 0
+    hits, n_total = p.find_entities_along_segments(seg, capacity=7)
+    assert n_total == len(want) and len(hits) == 7 and len(set(records_of(hits))) == 7 and set(records_of(hits)) <= set(want)
+    assert ask(p, p0, p1)[0] == want
+    # refused batches name the segment and leave the world alone: the next correct call answers
+    bad = both.copy(); bad[3, 4] = np.nan
+    expect_error(R, RE_E_ARG, "segment 3", p.find_entities_along_segments, bad)
+    bad = both.copy(); bad[5, 0] = np.inf
+    expect_error(R, RE_E_ARG, "segment 5", p.find_entities_along_segments, bad)
+    bad = both.copy(); bad[6, 0], bad[6, 3] = -3e38, 3e38                                            # finite endpoints, p1 - p0 is not
+    expect_error(R, RE_E_ARG, "segment 6", p.find_entities_along_segments, bad)
+    bad = both.copy(); bad[9] = [7000, 7000, 7000, 10000, 10000, 10000]
+    expect_error(R, RE_E_ARG, "segment 9", p.find_entities_along_segments, bad)
+    bad = seg.copy(); bad["reserved"][11] = 1
+    expect_error(R, RE_E_ARG, "segment 11", p.find_entities_along_segments, bad)
+    args = L.BoxQueryArgs(0, 0); args.reserved[1] = 1
+    assert lib.re_query_segments(p._h, seg.ctypes.data, len(seg), C.byref(args), None, 0, C.byref(n)) == RE_E_ARG
+    assert b"reserved" in lib.re_last_error(p._h)
+    assert lib.re_query_segments(p._h, seg.ctypes.data, len(seg), None, None, 4, C.byref(n)) == RE_E_ARG          # capacity without a buffer
+    assert lib.re_query_segments(p._h, seg.ctypes.data, L.BOX_QUERY_MAX_QUERIES + 1, None, None, 0, C.byref(n)) == RE_E_ARG
+    assert ask(p, p0, p1)[0] == want
+    # an axis-aligned segment may be far longer than a diagonal one: across the whole world
+    long0, long1 = np.array([[100, 8192, 8192]], F32), np.array([[16000, 8192, 8192]], F32)
+    assert ask(p, long0, long1)[0] == segment_hits(w, ids, long0, long1)
+    # 4096 identical segments: every query index appears, with the same set (the staging overflow path; more than one tile of the shared part)
+    q0 = max(range(16), key=lambda i: sum(1 for r in want if r[0] == i))
+    rec0 = sorted(r[1:] for r in want if r[0] == q0)
+    assert len(rec0) > 0
+    hits, n_total = p.find_entities_along_segments(np.repeat(both[q0:q0 + 1], 4096, axis=0))
+    assert n_total == 4096 * len(rec0) == len(hits)
+    order = np.lexsort((hits["entity_id"], hits["query"]))
+    np.testing.assert_array_equal(hits["query"][order], np.repeat(np.arange(4096, dtype=np.uint32), len(rec0)))
+    np.testing.assert_array_equal(hits["entity_id"][order], np.tile(np.array([r[0] for r in rec0], np.uint32), 4096))
+    np.testing.assert_array_equal(hits["t_enter"][order].view(np.uint32), np.tile(np.array([r[1] for r in rec0], np.uint32), 4096))
+    np.testing.assert_array_equal(hits["t_exit"][order].view(np.uint32), np.tile(np.array([r[2] for r in rec0], np.uint32), 4096))
+    # a second context in the same process, unaffected and unaffecting
+    p2, w2 = build_pair(R, probe_world(64))
+    a, b = np.array([[0, 15, 15]], F32), np.array([[128, 15, 15]], F32)
+    assert [r[:2] for r in ask(p2, a, b)[0]] == [(0, 0), (0, 1), (0, 2), (0, 4)] == [r[:2] for r in segment_hits(w2, range(6), a, b)]
+    assert ask(p, p0, p1)[0] == want
+    assert ask(p2, a, b)[1] == 4
+    assert_clean_publication(p); assert_clean_publication(p2)
+    p2.close(); w2.close(); p.close(); w.close()
+
+
+def test_sample_scene_shot_at_the_mine_producer(R):
+    """the 45-entity sample scene: a segment from the user entity (excluded) towards the mine producer; the first hit is the rule's"""
+    from test_sample_scene import scene
+    ents, world, camd = scene()
+    p, w = build_pair(R, ents, outline=world["outline_length"], atomic=world["atomic_length"])
+    ids = [int(i) for i in ents["id"]]
+    a = w.entity(0)["aabb"].reshape(3, 2).mean(axis=1)[None, :].astype(F32)
+    b = w.entity(44)["aabb"].reshape(3, 2).mean(axis=1)[None, :].astype(F32)
+    ex = np.array([0], np.uint32)
+    want = segment_hits(w, ids, a, b, exclude=ex)
+    assert (0, 44) in [r[:2] for r in want] and (0, 0) not in [r[:2] for r in want]
+    assert (0, 0) in [r[:2] for r in segment_hits(w, ids, a, b)]                   # (unexcluded, the shooter is its own first hit)
+    for _ in range(2):
+        hits, n_total = p.find_entities_along_segments(np.concatenate([a, b], axis=1), exclude=ex)
+        assert records_of(hits) == want and n_total == len(want)
+        first, found = R.first_hits(hits, 1)
+        assert found[0] and records_of(first) == [first_hits_brute(want, 1)[0]]
+        p.cull_and_pack(R.Camera(camd["position"], camd["direction"], camd["far"]))
+    assert_clean_publication(p)
+    p.close(); w.close()
+
+
+def test_cpp_mirror_find_entities_along_segments():
+    """include/render_engine_hip.hpp: Pipeline::find_entities_along_segments and first_hits -- before the first frame, with the shooter excluded, filtered,
+    with an instance registered after frames have run, a segment that ends on a face (tests/cpp/segment_query_shim_test.cpp)"""
+    import os
+    import subprocess
+    from render_engine_amd import build as libbuild
+    here = os.path.dirname(os.path.abspath(__file__))
+    exe = os.path.join(here, "cpp", "_build", "segment_query_shim_test")
+    lib_dir = os.path.dirname(libbuild.build_library())
+    os.makedirs(os.path.dirname(exe), exist_ok=True)
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-Werror", "-I", os.path.join(os.path.dirname(here), "include"),
+                           os.path.join(here, "cpp", "segment_query_shim_test.cpp"), "-o", exe, "-L", lib_dir, "-lrender_engine_hip", "-Wl,-rpath," + lib_dir])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "OK segment queries" in out.stdout, out.stdout + out.stderr
