@@ -73,7 +73,7 @@ typedef struct re_ctx re_ctx;
 typedef struct {
     int32_t  device;            /* HIP device ordinal */
     uint32_t outline_length;    /* BoundingBoxTree::new(outline, atomic): 16384 in render_thread.rs:127 */
-    uint32_t atomic_length;     /* world_section_length: 64 (load_models.rs:52) */
+    uint32_t atomic_length;     /* world_section_length: 64 (load_models.rs:52); any length >= 1, a power of two or not (96 is tested) */
     uint32_t max_instances;     /* capacity of the packed instance buffer, in instances (0 = number of entities) */
     uint32_t flags;             /* RE_CFG_* */
 } re_config;

@@ -27,7 +27,10 @@
  * sin/cos: the reference calls f32::sin_cos (platform libm, <=1 ulp, platform dependent).
  * The oracle and the HIP kernels share one deterministic evaluation (ro_sincosf: f64
  * Cody-Waite reduction + fdlibm kernel polynomials, rounded once to f32), so the GPU can be
- * compared bit-for-bit with the oracle while both stay within 1 ulp of any libm.
+ * compared bit-for-bit with the oracle.  Both are within 1 f32 ulp of the exact value for
+ * |x| < 1e6; up to 2^26 the absolute error is at most 2^-25 + |x| * 3.9e-17 (the fmod by
+ * the double 2 pi drifts by 2.449e-16 per turn); beyond 2^26 only finite values in [-1, 1]
+ * are promised (re_math.h: sincos_det).
  */
 #ifndef RE_ORACLE_H
 #define RE_ORACLE_H
