@@ -87,6 +87,15 @@ struct ListChannel {
     int wait(re_ctx *c, uint32_t seq, uint32_t *n);       // completion of call `seq`: polls the sequence number the last workgroup publishes (a stream synchronise costs tens of microseconds)
     void close() { if (h_pub) { (void)hipHostFree(h_pub); h_pub = d_pub = nullptr; } hdr.release(nullptr); }
 };
+// One kind of tree query (re_query_boxes, re_query_segments): the batch travels from two pinned buffers that alternate by call into one device array; records
+// come back through d_out; header block, mapped block and sequence numbers of its own.  Allocated lazily, kept across uploads.
+template <class Query> struct QueryFlow {
+    Query *h_q[2] = {}; size_t h_cap[2] = {}; uint32_t k = 0; DevBuf<Query> d_q; DevBuf<unsigned long long> d_out; ListChannel ch;
+    void release() {
+        ch.close(); d_q.release(nullptr); d_out.release(nullptr);
+        for (int i = 0; i < 2; i++) if (h_q[i]) { (void)hipHostFree(h_q[i]); h_q[i] = nullptr; h_cap[i] = 0; }
+    }
+};
 struct re_ctx {
     re_config cfg{};
     int device = 0;
@@ -273,10 +282,7 @@ struct re_ctx {
     std::vector<uint64_t> h_type; std::vector<uint8_t> h_typed;                // [row]; rows beyond the vectors carry no type
     std::vector<re_entity_logic> logic_table; std::unordered_map<uint64_t, uint32_t> logic_index;   // TypeIdentifier -> table index
     DevBuf<uint32_t> d_logic_rows, d_logic_words; DevBuf<unsigned long long> d_logic_out; ListChannel logic; uint32_t logic_n = 0; bool logic_dirty = true;
-    // tree queries (re_query_boxes): the batch travels from two pinned buffers that alternate by call into one device array; records come back through d_boxq_out
-    BoxQuery *h_boxq[2] = {}; size_t h_boxq_cap[2] = {}; uint32_t boxq_k = 0; DevBuf<BoxQuery> d_boxq; DevBuf<unsigned long long> d_boxq_out; ListChannel boxq;
-    // ... and re_query_segments: the same arrangement with buffers, header block, mapped block and sequence numbers of its own
-    SegQuery *h_segq[2] = {}; size_t h_segq_cap[2] = {}; uint32_t segq_k = 0; DevBuf<SegQuery> d_segq; DevBuf<unsigned long long> d_segq_out; ListChannel segq;
+    QueryFlow<BoxQuery> boxq; QueryFlow<SegQuery> segq;                        // tree queries (re_query_boxes, re_query_segments)
 };
 
 #define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return (ctx)->fail(RE_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
@@ -380,10 +386,7 @@ static void drop_collision_scratch(re_ctx *c) { c->d_row_moved.release(nullptr);
 static void release_flows(re_ctx *c) {
     c->d_col_hdr.release(nullptr); c->d_col_region.release(nullptr); c->d_col_high.release(nullptr); c->d_col_shared.release(nullptr); c->d_col_near.release(nullptr); c->d_col_pairs.release(nullptr); c->col_pair_cap = 0; drop_collision_scratch(c);
     if (c->h_col) { (void)hipHostFree(c->h_col); c->h_col = c->d_hcol = nullptr; }
-    c->logic.close(); c->boxq.close(); c->d_boxq.release(nullptr); c->d_boxq_out.release(nullptr);
-    for (int k = 0; k < 2; k++) if (c->h_boxq[k]) { (void)hipHostFree(c->h_boxq[k]); c->h_boxq[k] = nullptr; c->h_boxq_cap[k] = 0; }
-    c->segq.close(); c->d_segq.release(nullptr); c->d_segq_out.release(nullptr);
-    for (int k = 0; k < 2; k++) if (c->h_segq[k]) { (void)hipHostFree(c->h_segq[k]); c->h_segq[k] = nullptr; c->h_segq_cap[k] = 0; }
+    c->logic.close(); c->boxq.release(); c->segq.release();
 }
 static void free_world(re_ctx *c) {
     uint64_t *a = &c->dev_bytes;
@@ -4091,6 +4094,13 @@ static int sync_logic_rows(re_ctx *c) {
     return RE_OK;
 }
 
+// the end of a record-list call behind ListChannel::wait (re_logic_list, the tree queries): the records the caller's buffer holds, and the total
+static int read_out_list(re_ctx *c, uint32_t nrec, const void *d_records, size_t record_bytes, void *records, uint32_t capacity, uint32_t *n_total) {
+    const uint32_t nw = std::min(nrec, capacity);
+    if (nw) HIPCHK(c, hipMemcpy(records, d_records, (size_t)nw * record_bytes, hipMemcpyDeviceToHost));
+    if (n_total) *n_total = nrec;
+    return RE_OK;
+}
 static_assert(sizeof(re_logic_call) == 8 && sizeof(re_entity_logic) == 16, "record layouts of include/re_hip.h");
 extern "C" int re_logic_list(re_ctx *c, uint32_t flags, re_logic_call *calls, uint32_t capacity, uint32_t *n_total) try {
     if (!c) return RE_E_ARG;
@@ -4113,15 +4123,12 @@ extern "C" int re_logic_list(re_ctx *c, uint32_t flags, re_logic_call *calls, ui
     uint32_t nrec = 0;
     { int rc = c->logic.wait(c, seq, &nrec); if (rc != RE_OK) return rc; }
     if (nrec > c->logic_n) return c->fail(RE_E_HIP, "re_logic_list: %u records from %u listed rows", nrec, c->logic_n);
-    const uint32_t nw = std::min(nrec, capacity);
-    if (nw) HIPCHK(c, hipMemcpy(calls, c->d_logic_out.p, (size_t)nw * sizeof(re_logic_call), hipMemcpyDeviceToHost));
-    if (n_total) *n_total = nrec;
-    return RE_OK;
+    return read_out_list(c, nrec, c->d_logic_out.p, sizeof(re_logic_call), calls, capacity, n_total);
 } RE_ABI_GUARD(c, "re_logic_list")
 
 // ------------------------------------------------------------------------------------------------
 // Tree queries for user logic: what a LogicFunction / CollisionFunction / UserInputLogicFunction reads out of its &BoundingBoxTree
-// (exports/logic_components.rs:14-18) -- the entities in a batch of boxes (k_box_query, re_boxquery.hip).  The tree lives on the device only.
+// (exports/logic_components.rs:14-18) -- the entities in a batch of boxes and along a batch of segments (k_box_query, k_segment_query: re_treequery.hip).  The tree lives on the device only.
 // ------------------------------------------------------------------------------------------------
 static_assert(sizeof(re_box_hit) == 8 && sizeof(re_box_query_args) == 16 && sizeof(BoxQuery) == 64, "record layouts of include/re_hip.h / re_kernels.h");
 // one box as the kernel gets it; the candidate cells of all levels, counted with the kernel's own arithmetic (box_level_range)
@@ -4140,93 +4147,85 @@ static uint64_t make_box_query(const float *b, uint32_t outline, uint32_t atomic
     q->ncells = (uint32_t)std::min<uint64_t>(cells, 0xFFFFFFFFull);
     return cells;
 }
-extern "C" int re_query_boxes(re_ctx *c, const float *boxes6, uint32_t n, const re_box_query_args *args, re_box_hit *hits, uint32_t capacity, uint32_t *n_total) try {
-    if (!c) return RE_E_ARG;
-    if (n > RE_BOX_QUERY_MAX_QUERIES) return c->fail(RE_E_ARG, "re_query_boxes: %u boxes (at most %u a call)", n, RE_BOX_QUERY_MAX_QUERIES);
-    if (n && !boxes6) return c->fail(RE_E_ARG, "re_query_boxes: boxes6 is NULL");
-    if (capacity && !hits) return c->fail(RE_E_ARG, "re_query_boxes: capacity without a buffer");
-    if (args && (args->reserved[0] || args->reserved[1])) return c->fail(RE_E_ARG, "re_query_boxes: reserved must be 0");
-    if (!c->h_res) return c->fail(RE_E_STATE, "re_query_boxes: no world uploaded");
-    if (c->cfg.outline_length > (1u << 30)) return c->fail(RE_E_UNSUPPORTED, "re_query_boxes: outline lengths beyond 2^30 are not supported (32-bit cell arithmetic)");
+// What the two calls share, from the argument checks to *n_total.  `call`, `plural`, `argument`: the names in the messages; build(i, &q) checks query i and
+// writes its record, or fails naming it; rec_words: 8-byte words of an output record; A: the kernel's argument block with the kernel's own members set.
+template <class Query, class KArgs, class Build>
+static int run_tree_query(re_ctx *c, const char *call, const char *plural, const char *argument, QueryFlow<Query> &F, const void *queries, uint32_t n, const re_box_query_args *args,
+                          void *hits, uint32_t capacity, uint32_t *n_total, Build build, uint32_t rec_words, void (*kernel)(KArgs), KArgs A) {
+    if (n > RE_BOX_QUERY_MAX_QUERIES) return c->fail(RE_E_ARG, "%s: %u %s (at most %u a call)", call, n, plural, RE_BOX_QUERY_MAX_QUERIES);
+    if (n && !queries) return c->fail(RE_E_ARG, "%s: %s is NULL", call, argument);
+    if (capacity && !hits) return c->fail(RE_E_ARG, "%s: capacity without a buffer", call);
+    if (args && (args->reserved[0] || args->reserved[1])) return c->fail(RE_E_ARG, "%s: reserved must be 0", call);
+    if (!c->h_res) return c->fail(RE_E_STATE, "%s: no world uploaded", call);
+    if (c->cfg.outline_length > (1u << 30)) return c->fail(RE_E_UNSUPPORTED, "%s: outline lengths beyond 2^30 are not supported (32-bit cell arithmetic)", call);
     if (n_total) *n_total = 0;
     if (n == 0) return RE_OK;
-    // the batch, checked whole before anything is touched: built in the pinned buffer that was not the last call's source
-    const uint32_t k = c->boxq_k ^= 1u;
-    if (c->h_boxq_cap[k] < n) {
-        if (c->h_boxq[k]) { (void)hipHostFree(c->h_boxq[k]); c->h_boxq[k] = nullptr; c->h_boxq_cap[k] = 0; }
+    // the batch, checked whole before anything is touched: built in the pinned buffer that was not the last call's source (a refused batch is never launched:
+    // only what this call has built in full is copied to the device)
+    const uint32_t k = F.k ^= 1u;
+    if (F.h_cap[k] < n) {
+        if (F.h_q[k]) { (void)hipHostFree(F.h_q[k]); F.h_q[k] = nullptr; F.h_cap[k] = 0; }
         const size_t cap = std::max<size_t>((size_t)n + n / 2, 256);
         HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_boxq[k]), cap * sizeof(BoxQuery), hipHostMallocDefault));
-        c->h_boxq_cap[k] = cap;
+        HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&F.h_q[k]), cap * sizeof(Query), hipHostMallocDefault));
+        F.h_cap[k] = cap;
     }
-    BoxQuery *hq = c->h_boxq[k];
-    for (uint32_t i = 0; i < n; i++) {
-        const float *b = boxes6 + (size_t)i * 6;
-        for (int a = 0; a < 3; a++) {
-            if (b[2 * a] != b[2 * a] || b[2 * a + 1] != b[2 * a + 1]) return c->fail(RE_E_ARG, "re_query_boxes: box %u has a NaN", i);
-            if (b[2 * a] > b[2 * a + 1]) return c->fail(RE_E_ARG, "re_query_boxes: box %u is inverted (min > max on an axis)", i);
-        }
-        const uint64_t cells = make_box_query(b, c->cfg.outline_length, c->cfg.atomic_length, c->maxlevel, &hq[i]);
-        if (cells > RE_BOX_QUERY_MAX_CELLS) return c->fail(RE_E_ARG, "re_query_boxes: box %u covers %llu candidate cells (at most %u; a sweep of the world is re_ecs_query's)", i, (unsigned long long)cells, RE_BOX_QUERY_MAX_CELLS);
-    }
+    Query *hq = F.h_q[k];
+    for (uint32_t i = 0; i < n; i++) { int rc = build(i, &hq[i]); if (rc != RE_OK) return rc; }
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = settle_frame(c); if (rc != RE_OK) return rc; }                  // (an asynchronous cull or tick in flight is finished first; the query reads no frame stamps)
     if (!c->n || !c->ncells) return RE_OK;                                     // a world without rows
     { int rc = ensure_device_lookup(c, true); if (rc != RE_OK) return rc; }
     hipStream_t st = c->stream;
-    { int rc = c->boxq.open(c); if (rc != RE_OK) return rc; }
+    { int rc = F.ch.open(c); if (rc != RE_OK) return rc; }
     const uint32_t cap_dev = (uint32_t)std::min<uint64_t>(capacity, (uint64_t)n * c->n);      // (no more pairs than queries x rows exist)
-    if (c->d_boxq.n < n || !c->d_boxq.p || c->d_boxq_out.n < cap_dev || !c->d_boxq_out.p) {      // a buffer that must grow is replaced only after the stream has drained
+    const size_t out_words = (size_t)cap_dev * rec_words;
+    if (F.d_q.n < n || !F.d_q.p || F.d_out.n < out_words || !F.d_out.p) {      // a buffer that must grow is replaced only after the stream has drained
         HIPCHK(c, sync_stream(st));
-        if (c->d_boxq.n < n || !c->d_boxq.p) HIPCHK(c, c->d_boxq.alloc((size_t)n + n / 2, nullptr));
-        if (c->d_boxq_out.n < cap_dev || !c->d_boxq_out.p) HIPCHK(c, c->d_boxq_out.alloc((size_t)cap_dev + cap_dev / 2, nullptr));
+        if (F.d_q.n < n || !F.d_q.p) HIPCHK(c, F.d_q.alloc((size_t)n + n / 2, nullptr));
+        if (F.d_out.n < out_words || !F.d_out.p) HIPCHK(c, F.d_out.alloc(((size_t)cap_dev + cap_dev / 2) * rec_words, nullptr));
     }
-    HIPCHK(c, hipMemcpyAsync(c->d_boxq.p, hq, (size_t)n * sizeof(BoxQuery), hipMemcpyHostToDevice, st));
-    BoxQueryArgs A{};
+    HIPCHK(c, hipMemcpyAsync(F.d_q.p, hq, (size_t)n * sizeof(Query), hipMemcpyHostToDevice, st));
     A.n = n; A.n_sh_chunks = c->nsh ? (c->nsh + BOXQ_THREADS - 1u) / BOXQ_THREADS : 0u;
     A.atomic = c->cfg.atomic_length; A.max_level = c->maxlevel; A.need = args ? args->need_flags : 0u; A.forbid = args ? args->forbid_flags : 0u; A.nrows = c->n; A.capacity = cap_dev;
-    A.q = c->d_boxq.p; A.T = rb_tables(c); A.cell_key = c->d_cell_key.p; A.cell_begin = c->d_cell_begin.p; A.cell_nl = c->d_cell_nlocal.p; A.cell_ns = c->d_cell_nstatic.p; A.rows = c->d_rows.p;
+    A.q = F.d_q.p; A.T = rb_tables(c); A.cell_key = c->d_cell_key.p; A.cell_begin = c->d_cell_begin.p; A.cell_nl = c->d_cell_nlocal.p; A.cell_ns = c->d_cell_nstatic.p; A.rows = c->d_rows.p;
     A.row_flags = c->d_flags.p; A.row_id = c->d_id.p; A.row_cell = c->d_row_cell.p; A.row_aabb = c->d_aabb.p;
     A.nsh = c->nsh; A.sh_keys = c->d_sh_keys.p; A.sh_nk = c->d_sh_nk.p; A.sh_begin = c->d_sh_begin.p; A.sh_nact = c->d_sh_nact.p; A.sh_nstat = c->d_sh_nstat.p;
-    A.hdr = c->boxq.hdr.p; A.out = c->d_boxq_out.p; A.h_pub = c->boxq.d_pub; A.seq = c->boxq.next_seq();
+    A.hdr = F.ch.hdr.p; A.out = F.d_out.p; A.h_pub = F.ch.d_pub; A.seq = F.ch.next_seq();
     const uint32_t grid = n + A.n_sh_chunks * ((n + BOXQ_TILE - 1u) / BOXQ_TILE);
-    hipLaunchKernelGGL(k_box_query, dim3(grid), dim3(BOXQ_THREADS), 0, st, A);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(BOXQ_THREADS), 0, st, A);
     HIPCHK(c, hipGetLastError());
     uint32_t nrec = 0;
-    { int rc = c->boxq.wait(c, A.seq, &nrec); if (rc != RE_OK) return rc; }
-    const uint32_t nw = std::min(nrec, cap_dev);
-    if (nw) HIPCHK(c, hipMemcpy(hits, c->d_boxq_out.p, (size_t)nw * sizeof(re_box_hit), hipMemcpyDeviceToHost));
-    if (n_total) *n_total = nrec;
-    return RE_OK;
+    { int rc = F.ch.wait(c, A.seq, &nrec); if (rc != RE_OK) return rc; }
+    return read_out_list(c, nrec, F.d_out.p, rec_words * sizeof(unsigned long long), hits, cap_dev, n_total);
+}
+
+extern "C" int re_query_boxes(re_ctx *c, const float *boxes6, uint32_t n, const re_box_query_args *args, re_box_hit *hits, uint32_t capacity, uint32_t *n_total) try {
+    if (!c) return RE_E_ARG;
+    auto build = [&](uint32_t i, BoxQuery *q) {
+        const float *b = boxes6 + (size_t)i * 6;
+        for (int a = 0; a < 3; a++) {
+            if (b[2 * a] != b[2 * a] || b[2 * a + 1] != b[2 * a + 1]) return c->fail(RE_E_ARG, "re_query_boxes: box %u has a NaN", i);
+            if (b[2 * a] > b[2 * a + 1]) return c->fail(RE_E_ARG, "re_query_boxes: box %u is inverted (min > max on an axis)", i);
+        }
+        const uint64_t cells = make_box_query(b, c->cfg.outline_length, c->cfg.atomic_length, c->maxlevel, q);
+        if (cells > RE_BOX_QUERY_MAX_CELLS) return c->fail(RE_E_ARG, "re_query_boxes: box %u covers %llu candidate cells (at most %u; a sweep of the world is re_ecs_query's)", i, (unsigned long long)cells, RE_BOX_QUERY_MAX_CELLS);
+        return (int)RE_OK;
+    };
+    return run_tree_query(c, "re_query_boxes", "boxes", "boxes6", c->boxq, boxes6, n, args, hits, capacity, n_total, build, 1u, k_box_query, BoxQueryArgs{});
 } RE_ABI_GUARD(c, "re_query_boxes")
 
-// ... and the entities along a batch of segments (k_segment_query, re_segquery.hip): the same contract, the same record-list protocol on a channel of its own
+// ... and the entities along a batch of segments (k_segment_query): the same contract, the same record-list protocol on a channel of its own
 static_assert(sizeof(re_segment) == 32 && sizeof(re_segment_hit) == 16 && sizeof(SegQuery) == 64, "record layouts of include/re_hip.h / re_kernels.h");
 extern "C" int re_query_segments(re_ctx *c, const re_segment *segments, uint32_t n, const re_box_query_args *args, re_segment_hit *hits, uint32_t capacity, uint32_t *n_total) try {
     if (!c) return RE_E_ARG;
-    if (n > RE_BOX_QUERY_MAX_QUERIES) return c->fail(RE_E_ARG, "re_query_segments: %u segments (at most %u a call)", n, RE_BOX_QUERY_MAX_QUERIES);
-    if (n && !segments) return c->fail(RE_E_ARG, "re_query_segments: segments is NULL");
-    if (capacity && !hits) return c->fail(RE_E_ARG, "re_query_segments: capacity without a buffer");
-    if (args && (args->reserved[0] || args->reserved[1])) return c->fail(RE_E_ARG, "re_query_segments: reserved must be 0");
-    if (!c->h_res) return c->fail(RE_E_STATE, "re_query_segments: no world uploaded");
-    if (c->cfg.outline_length > (1u << 30)) return c->fail(RE_E_UNSUPPORTED, "re_query_segments: outline lengths beyond 2^30 are not supported (32-bit cell arithmetic)");
-    if (n_total) *n_total = 0;
-    if (n == 0) return RE_OK;
-    // the batch, checked whole before anything is touched: built in the pinned buffer that was not the last call's source
-    const uint32_t k = c->segq_k ^= 1u;
-    if (c->h_segq_cap[k] < n) {
-        if (c->h_segq[k]) { (void)hipHostFree(c->h_segq[k]); c->h_segq[k] = nullptr; c->h_segq_cap[k] = 0; }
-        const size_t cap = std::max<size_t>((size_t)n + n / 2, 256);
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_segq[k]), cap * sizeof(SegQuery), hipHostMallocDefault));
-        c->h_segq_cap[k] = cap;
-    }
-    SegQuery *hq = c->h_segq[k];
-    const float margin = segment_query_margin(c->cfg.outline_length);
-    for (uint32_t i = 0; i < n; i++) {
+    SegQueryArgs A{};
+    A.outline = c->cfg.outline_length; A.margin = segment_query_margin(c->cfg.outline_length);
+    const float margin = A.margin;
+    auto build = [&](uint32_t i, SegQuery *out) {
         const re_segment &s = segments[i];
         if (s.reserved) return c->fail(RE_E_ARG, "re_query_segments: segment %u: reserved must be 0", i);
-        SegQuery &q = hq[i];
+        SegQuery &q = *out;
         float bb[6];
         for (int a = 0; a < 3; a++) {
             float d = s.p1[a] - s.p0[a];
@@ -4241,35 +4240,7 @@ extern "C" int re_query_segments(re_ctx *c, const re_segment *segments, uint32_t
         if (cells > RE_BOX_QUERY_MAX_CELLS) return c->fail(RE_E_ARG, "re_query_segments: the bounding box of segment %u covers %llu candidate cells (at most %u: about 30 atomic lengths per axis for a diagonal)", i, (unsigned long long)cells, RE_BOX_QUERY_MAX_CELLS);
         q.exclude = s.exclude_entity; q.flags = b.flags; q.ncells = b.ncells; q.pad = 0;
         for (int a = 0; a < 3; a++) { q.umin[a] = b.umin[a]; q.umax[a] = b.umax[a]; }
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    { int rc = settle_frame(c); if (rc != RE_OK) return rc; }                  // (an asynchronous cull or tick in flight is finished first; the query reads no frame stamps)
-    if (!c->n || !c->ncells) return RE_OK;                                     // a world without rows
-    { int rc = ensure_device_lookup(c, true); if (rc != RE_OK) return rc; }
-    hipStream_t st = c->stream;
-    { int rc = c->segq.open(c); if (rc != RE_OK) return rc; }
-    const uint32_t cap_dev = (uint32_t)std::min<uint64_t>(capacity, (uint64_t)n * c->n);      // (no more pairs than segments x rows exist)
-    if (c->d_segq.n < n || !c->d_segq.p || c->d_segq_out.n < (size_t)cap_dev * 2u || !c->d_segq_out.p) {      // a buffer that must grow is replaced only after the stream has drained
-        HIPCHK(c, sync_stream(st));
-        if (c->d_segq.n < n || !c->d_segq.p) HIPCHK(c, c->d_segq.alloc((size_t)n + n / 2, nullptr));
-        if (c->d_segq_out.n < (size_t)cap_dev * 2u || !c->d_segq_out.p) HIPCHK(c, c->d_segq_out.alloc(((size_t)cap_dev + cap_dev / 2) * 2u, nullptr));
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_segq.p, hq, (size_t)n * sizeof(SegQuery), hipMemcpyHostToDevice, st));
-    SegQueryArgs A{};
-    A.n = n; A.n_sh_chunks = c->nsh ? (c->nsh + BOXQ_THREADS - 1u) / BOXQ_THREADS : 0u;
-    A.atomic = c->cfg.atomic_length; A.max_level = c->maxlevel; A.need = args ? args->need_flags : 0u; A.forbid = args ? args->forbid_flags : 0u; A.nrows = c->n; A.capacity = cap_dev;
-    A.outline = c->cfg.outline_length; A.margin = margin;
-    A.q = c->d_segq.p; A.T = rb_tables(c); A.cell_key = c->d_cell_key.p; A.cell_begin = c->d_cell_begin.p; A.cell_nl = c->d_cell_nlocal.p; A.cell_ns = c->d_cell_nstatic.p; A.rows = c->d_rows.p;
-    A.row_flags = c->d_flags.p; A.row_id = c->d_id.p; A.row_cell = c->d_row_cell.p; A.row_aabb = c->d_aabb.p;
-    A.nsh = c->nsh; A.sh_keys = c->d_sh_keys.p; A.sh_nk = c->d_sh_nk.p; A.sh_begin = c->d_sh_begin.p; A.sh_nact = c->d_sh_nact.p; A.sh_nstat = c->d_sh_nstat.p;
-    A.hdr = c->segq.hdr.p; A.out = c->d_segq_out.p; A.h_pub = c->segq.d_pub; A.seq = c->segq.next_seq();
-    const uint32_t grid = n + A.n_sh_chunks * ((n + BOXQ_TILE - 1u) / BOXQ_TILE);
-    hipLaunchKernelGGL(k_segment_query, dim3(grid), dim3(BOXQ_THREADS), 0, st, A);
-    HIPCHK(c, hipGetLastError());
-    uint32_t nrec = 0;
-    { int rc = c->segq.wait(c, A.seq, &nrec); if (rc != RE_OK) return rc; }
-    const uint32_t nw = std::min(nrec, cap_dev);
-    if (nw) HIPCHK(c, hipMemcpy(hits, c->d_segq_out.p, (size_t)nw * sizeof(re_segment_hit), hipMemcpyDeviceToHost));
-    if (n_total) *n_total = nrec;
-    return RE_OK;
+        return (int)RE_OK;
+    };
+    return run_tree_query(c, "re_query_segments", "segments", "segments", c->segq, segments, n, args, hits, capacity, n_total, build, 2u, k_segment_query, A);
 } RE_ABI_GUARD(c, "re_query_segments")

@@ -426,7 +426,7 @@ __device__ __forceinline__ void rb_ovl_put(const RbTables &T, uint64_t key, uint
     }
 }
 #endif
-// tree queries for user logic (re_boxquery.hip): the entities whose StaticAABB intersects each box of a batch
+// tree queries for user logic (re_treequery.hip): the entities whose StaticAABB intersects each box of a batch
 // One query as the host builds it (re_query_boxes): the box as given (the exact test runs on it), and the box clipped to the world (normalize_aabb) as
 // integers -- umin / umax = the clipped bounds truncated, flags bit a = the clipped minimum of axis a (x, y, z) is a whole number.  The cell range of
 // every level follows from these by integer arithmetic alone (box_level_range), on the host (candidate count, the cap) and in the kernel alike.
@@ -444,33 +444,32 @@ constexpr uint32_t BOXQ_THREADS = 256, BOXQ_PROBES = 4;      // probes a lane ma
 constexpr uint32_t BOXQ_QUEUE = BOXQ_THREADS * BOXQ_PROBES;   // hit sections of one round (each probe yields at most one)
 constexpr uint32_t BOXQ_HITBUF = 1024;                        // records a workgroup stages in LDS between two flushes (more go out one wave at a time)
 constexpr uint32_t BOXQ_TILE = 256;                           // queries a workgroup of the shared part tests its 256 shared sections against
-struct BoxQueryArgs {
-    uint32_t n, n_sh_chunks;                // queries; 256-entry chunks of the shared table (the grid: n workgroups, then n_sh_chunks per tile of BOXQ_TILE queries)
-    uint32_t atomic, max_level, need, forbid, nrows, capacity;
-    const BoxQuery *q;
-    RbTables T; const uint64_t *cell_key; const uint32_t *cell_begin, *cell_nl, *cell_ns, *rows;
-    const uint32_t *row_flags, *row_id, *row_cell; const Aabb *row_aabb;
-    uint32_t nsh; const uint64_t *sh_keys; const uint8_t *sh_nk; const uint32_t *sh_begin, *sh_nact, *sh_nstat;
-    LogicHeader *hdr; unsigned long long *out; LogicPublished *h_pub; uint32_t seq;      // count, sign-off and publication as k_logic_list's (a block of its own)
-};
-__global__ void k_box_query(BoxQueryArgs A);
-// tree queries for user logic (re_segquery.hip): the entities along each segment of a batch
+// ... and the entities along each segment of a batch
 // One segment as the host builds it (re_query_segments): p0 and d = p1 - p0 (a subnormal component replaced by 0: the kernel never divides by one), the
 // excluded entity, and the segment's bounding box -- inflated by the margin -- as make_box_query leaves it: the candidate cells are that box's.
 struct SegQuery { float p0[3], d[3]; uint32_t exclude, umin[3], umax[3], flags, ncells, pad; };      // 64 bytes
 // The margin by which the prune inflates a cell's box (and the host the bounding box): outline * 2^-12.  The slab test's rounding error in world units is
 // bounded by about outline * 2^-21 -- three rounded operations on t <= 1 times |d| <= sqrt(3) * outline, plus the ulp of the coordinates.
 RE_HD float segment_query_margin(uint32_t outline) { return (float)outline * (1.0f / 4096.0f); }
-struct SegQueryArgs {
-    uint32_t n, n_sh_chunks;                // as BoxQueryArgs
+// The argument blocks of the two kernels: one head and one tail, and between them what a kernel has of its own -- the query records, and the segment's
+// prune parameters.  (The head's eight words lead: the build preloads the first kernel-argument dwords into SGPRs.)
+struct TreeQueryHead {
+    uint32_t n, n_sh_chunks;                // queries; 256-entry chunks of the shared table (the grid: n workgroups, then n_sh_chunks per tile of BOXQ_TILE queries)
     uint32_t atomic, max_level, need, forbid, nrows, capacity;
-    uint32_t outline; float margin;
-    const SegQuery *q;
+};
+struct TreeQueryWorld {
     RbTables T; const uint64_t *cell_key; const uint32_t *cell_begin, *cell_nl, *cell_ns, *rows;
     const uint32_t *row_flags, *row_id, *row_cell; const Aabb *row_aabb;
     uint32_t nsh; const uint64_t *sh_keys; const uint8_t *sh_nk; const uint32_t *sh_begin, *sh_nact, *sh_nstat;
-    LogicHeader *hdr; unsigned long long *out; LogicPublished *h_pub; uint32_t seq;      // out: two words a record (re_segment_hit)
+    LogicHeader *hdr; unsigned long long *out; LogicPublished *h_pub; uint32_t seq;      // count, sign-off and publication as k_logic_list's (a block of its own); out: one word a box record, two a segment's
 };
+struct BoxQueryOwn { const BoxQuery *q; };
+struct SegQueryOwn { uint32_t outline; float margin; const SegQuery *q; };
+struct BoxQueryArgs : TreeQueryHead, BoxQueryOwn, TreeQueryWorld {};
+struct SegQueryArgs : TreeQueryHead, SegQueryOwn, TreeQueryWorld {};
+static_assert(sizeof(BoxQueryArgs) == sizeof(TreeQueryHead) + sizeof(BoxQueryOwn) + sizeof(TreeQueryWorld) && sizeof(SegQueryArgs) == sizeof(TreeQueryHead) + sizeof(SegQueryOwn) + sizeof(TreeQueryWorld),
+              "the parts lie one behind the other, without padding");
+__global__ void k_box_query(BoxQueryArgs A);
 __global__ void k_segment_query(SegQueryArgs A);
 hipError_t sort_pairs_u64_u32(void *tmp, size_t *tmp_bytes, const uint64_t *keys_in, uint64_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out,
                               uint32_t n, unsigned begin_bit, unsigned end_bit, hipStream_t stream);      // re_sort.hip (rocPRIM radix sort)

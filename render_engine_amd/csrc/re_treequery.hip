@@ -1,0 +1,342 @@
+// Tree queries for user logic on the resident world, for gfx950 -- what a LogicFunction / CollisionFunction / UserInputLogicFunction of the reference
+// (exports/logic_components.rs:14-18) reads out of its &BoundingBoxTree (find_all_unique_world_section_ids, stored_entities_indexes,
+// shared_section_indexes): "who is near this box" (k_box_query) and "who lies along this segment" -- a shot, a line of sight, a pick ray (k_segment_query).
+// One walk of the tree, written once over a query shape; the two kernels instantiate it.
+//
+// The rule of the boxes: (query i, entity) for every live entity in the tree (not F_DEAD, not an F_PHANTOM replica, row_cell set; ghost instances of the
+// frozen static cache are no entities) whose stored StaticAABB intersects box i by StaticAABB::intersect (aabb.rs:68-73: closed intervals, plain f32
+// compares), optionally filtered by flag bits.  Each pair once.
+// The rule of the segments: (query i, entity, t_enter, t_exit) for every entity the box query would consider other than the segment's excluded one whose
+// stored, unclipped StaticAABB is met by the segment p0 + t * d, t in [0, 1], by the slab test below: plain f32, IEEE division, closed intervals, d == 0 on
+// an axis a containment test.  Each pair once; tests/segment_rule.py restates it.
+//
+// The walk: an entity's sections are a function of its AABB clipped to the world (normalize_aabb); clipping is monotone per axis, so two
+// intersecting intervals still intersect after it, and every entity of the rule has a section key inside the query's cell range of that key's level
+// (box_level_range, re_kernels.h; tests/test_box_query_rule.py shows it against the oracle).  The exact test then runs on the stored boxes.  A segment
+// walks the cell ranges of its bounding box (inflated by the margin), with one test more in front of every probe: a candidate
+// cell is looked up only when the segment meets the cell's own box -- inflated by the margin, and open-ended on an axis where the cell lies on a face of
+// the world, because entities clipped to the world sit there and the exact test runs on unclipped boxes.
+//   unique sections: one workgroup per query enumerates the candidate cells of every level, prunes (segments), looks the remaining keys up (rb_find) and
+//     walks the rows of the sections that exist, one wave per section, one lane per row;
+//   shared sections: their links to the unique sections are not on the device, so they are taken from their own side: workgroups behind the first n
+//     hold 256 shared sections each, one per lane, and test them against a tile of queries in LDS -- a shared section is walked once for a query
+//     when ANY of its linked keys lies in the query's range (that is the dedupe) and the query's prune lets the bounding cell box of the linked keys
+//     through (segments; inflated, open-ended as above), by the lane that owns it.  O(shared sections x queries) integer tests.
+//
+// A shape is the query as a lane holds it (a small value type: it sits in LDS for the workgroup's own query, in registers during a walk) and supplies
+//   Args, Query, Rec, TILE_WORDS      the kernel's argument block, the host's query record, the output record, the words of a query in the LDS tile
+//   stage / to_tile / from_tile       the payload out of the query record: into LDS by the first lanes of a workgroup, into and out of the tile
+//   cell_box / misses                 the prune of a candidate cell and of a shared section's bounding cell box ([c0, c1] per axis in world units)
+//   test                              the exact test on a row's AABB and id, which fills the record
+//   store                             the record's write-through store below the capacity
+#include "re_kernels.h"
+
+namespace re {
+
+namespace {
+
+__device__ __forceinline__ uint32_t treeq_mbcnt(uint64_t mask) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+// ---- boxes ------------------------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool boxq_intersect(const Aabb &a, const float *q) {      // StaticAABB::intersect: a.min <= b.max && a.max >= b.min per axis
+    return a.xmin <= q[1] && a.xmax >= q[0] && a.ymin <= q[3] && a.ymax >= q[2] && a.zmin <= q[5] && a.zmax >= q[4];
+}
+struct BoxShape {
+    using Args = BoxQueryArgs; using Query = BoxQuery; using Rec = unsigned long long;      // re_box_hit: query | entity << 32
+    struct CellBox {};                                                                      // no prune: every candidate cell is probed
+    static constexpr uint32_t TILE_WORDS = 13;     // a query in the LDS tile of the shared part: umin[3], umax[3], flags, then the box itself (6 floats)
+    float box[6];
+    static __device__ __forceinline__ void stage(BoxShape &L, const Query &Q, uint32_t tid) { if (tid < 6u) L.box[tid] = Q.box[tid]; }
+    static __device__ __forceinline__ void to_tile(const Query &Q, uint32_t *t) { for (uint32_t a = 0; a < 6u; a++) t[a] = __float_as_uint(Q.box[a]); }
+    static __device__ __forceinline__ BoxShape from_tile(const uint32_t *t) {
+        BoxShape P;
+#pragma unroll
+        for (int a = 0; a < 6; a++) P.box[a] = __uint_as_float(t[a]);
+        return P;
+    }
+    static __device__ __forceinline__ CellBox cell_box(const Args &, const uint32_t *, const uint32_t *) { return {}; }
+    __device__ __forceinline__ bool misses(const CellBox &) const { return false; }
+    __device__ __forceinline__ bool test(const Aabb &a, const uint32_t *id, uint32_t query, Rec &rec) const {
+        if (!boxq_intersect(a, box)) return false;
+        rec = (unsigned long long)query | ((unsigned long long)*id << 32);
+        return true;
+    }
+    // Records are read by the host as soon as it has seen the count: write-through stores (sc1), as k_logic_list's.
+    static __device__ __forceinline__ void store(const Args &A, uint32_t slot, const Rec &rec) {
+        if (slot < A.capacity) __hip_atomic_store(&A.out[slot], rec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
+
+// ---- segments ---------------------------------------------------------------------------------------------------------------------------------------
+// one axis of the slab test; false: d == 0 and p outside [mn, mx]
+__device__ __forceinline__ bool segq_axis(float p, float d, float mn, float mx, float &lo, float &hi) {
+    if (d == 0.0f) return p >= mn && p <= mx;
+    float u = (mn - p) / d, v = (mx - p) / d;
+    if (u > v) { const float t = u; u = v; v = t; }
+    if (u > lo) lo = u;
+    if (v < hi) hi = v;
+    return true;
+}
+// the slab test of the segment p + t * d, t in [0, 1], with a closed box (bounds may be infinite; p and d are finite, so no NaN arises)
+__device__ __forceinline__ bool segq_slab(float px, float py, float pz, float dx, float dy, float dz, float x0, float x1, float y0, float y1, float z0, float z1,
+                                          float &lo, float &hi) {
+    lo = 0.0f; hi = 1.0f;
+    if (!segq_axis(px, dx, x0, x1, lo, hi)) return false;
+    if (!segq_axis(py, dy, y0, y1, lo, hi)) return false;
+    if (!segq_axis(pz, dz, z0, z1, lo, hi)) return false;
+    return lo <= hi;
+}
+// bounds of the cells [c0, c1] (world units) of one axis as the prune takes them: inflated by the margin, open-ended on a face of the world
+__device__ __forceinline__ float segq_cell_min(uint32_t c0, float margin) { return c0 == 0u ? -__builtin_inff() : (float)c0 - margin; }
+__device__ __forceinline__ float segq_cell_max(uint32_t c1, uint32_t outline, float margin) { return c1 >= outline ? __builtin_inff() : (float)c1 + margin; }
+
+struct SegRec { uint32_t query, id; float t0, t1; };      // re_segment_hit
+
+struct SegShape {
+    using Args = SegQueryArgs; using Query = SegQuery; using Rec = SegRec;
+    struct CellBox { float x0, x1, y0, y1, z0, z1; };
+    static constexpr uint32_t TILE_WORDS = 14;     // a segment in the LDS tile of the shared part: umin[3], umax[3], flags, p0[3], d[3], exclude
+    float p0[3], d[3]; uint32_t exclude;
+    static __device__ __forceinline__ void stage(SegShape &L, const Query &Q, uint32_t tid) {
+        if (tid < 3u) { L.p0[tid] = Q.p0[tid]; L.d[tid] = Q.d[tid]; }
+        if (tid == 3u) L.exclude = Q.exclude;
+    }
+    static __device__ __forceinline__ void to_tile(const Query &Q, uint32_t *t) {
+        for (uint32_t a = 0; a < 3u; a++) { t[a] = __float_as_uint(Q.p0[a]); t[3u + a] = __float_as_uint(Q.d[a]); }
+        t[6] = Q.exclude;
+    }
+    static __device__ __forceinline__ SegShape from_tile(const uint32_t *t) {
+        SegShape P;
+#pragma unroll
+        for (int a = 0; a < 3; a++) { P.p0[a] = __uint_as_float(t[a]); P.d[a] = __uint_as_float(t[3 + a]); }
+        P.exclude = t[6];
+        return P;
+    }
+    static __device__ __forceinline__ CellBox cell_box(const Args &A, const uint32_t *c0, const uint32_t *c1) {
+        return { segq_cell_min(c0[0], A.margin), segq_cell_max(c1[0], A.outline, A.margin), segq_cell_min(c0[1], A.margin), segq_cell_max(c1[1], A.outline, A.margin),
+                 segq_cell_min(c0[2], A.margin), segq_cell_max(c1[2], A.outline, A.margin) };
+    }
+    // the prune: the cell's closed box holds the clipped AABB of every entity of a unique section there (of a shared section: the bounding cell box does)
+    __device__ __forceinline__ bool misses(const CellBox &b) const {
+        float t0, t1;
+        return !segq_slab(p0[0], p0[1], p0[2], d[0], d[1], d[2], b.x0, b.x1, b.y0, b.y1, b.z0, b.z1, t0, t1);
+    }
+    __device__ __forceinline__ bool test(const Aabb &a, const uint32_t *id, uint32_t query, Rec &rec) const {
+        rec.query = query; rec.id = *id;
+        if (rec.id == exclude) return false;
+        return segq_slab(p0[0], p0[1], p0[2], d[0], d[1], d[2], a.xmin, a.xmax, a.ymin, a.ymax, a.zmin, a.zmax, rec.t0, rec.t1);
+    }
+    // write-through stores, as the box query's; two 8-byte halves, both below the capacity or neither
+    static __device__ __forceinline__ void store(const Args &A, uint32_t slot, const Rec &r) {
+        if (slot >= A.capacity) return;
+        unsigned long long *o = A.out + (size_t)slot * 2u;
+        __hip_atomic_store(o, (unsigned long long)r.query | ((unsigned long long)r.id << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(o + 1, (unsigned long long)__float_as_uint(r.t0) | ((unsigned long long)__float_as_uint(r.t1) << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
+
+// ---- the walk ---------------------------------------------------------------------------------------------------------------------------------------
+constexpr uint32_t TREEQ_TILE_HEAD = 7;        // every shape's tile entry starts with umin[3], umax[3], flags; the shape's payload follows
+
+template <class Shape> struct TreeqShared {
+    typename Shape::Rec hits[BOXQ_HITBUF];         // staged records
+    uint32_t queue[BOXQ_TILE * Shape::TILE_WORDS]; // unique part: slots of the hit sections of a round; shared part: the query tile
+    uint32_t n_hits, n_queue, gbase;
+    uint32_t prefix[MAX_LEVELS + 2], lo[3][MAX_LEVELS + 1], ext[3][MAX_LEVELS + 1];      // unique part: candidate cells before each level, first cell and extent per axis
+    Shape own;                                     // unique part: the workgroup's query
+    static_assert(BOXQ_QUEUE <= BOXQ_TILE * Shape::TILE_WORDS, "the section queue shares the LDS of the query tile");
+};
+
+// the staged records leave: ONE global atomicAdd per workgroup and flush.  Called by all 256 threads.
+template <class Shape> __device__ __forceinline__ void treeq_flush(const typename Shape::Args &A, TreeqShared<Shape> &S) {
+    __syncthreads();
+    const uint32_t n = S.n_hits < BOXQ_HITBUF ? S.n_hits : BOXQ_HITBUF;
+    if (n == 0u) return;                                                   // (uniform)
+    if (threadIdx.x == 0) S.gbase = atomicAdd(&A.hdr->count, n);
+    __syncthreads();
+    for (uint32_t k = threadIdx.x; k < n; k += BOXQ_THREADS) Shape::store(A, S.gbase + k, S.hits[k]);
+    __syncthreads();
+    if (threadIdx.x == 0) S.n_hits = 0u;
+    __syncthreads();
+}
+
+// is the row an entity of the tree that passes the filter?  expect: the row_cell word of a member of the section being walked
+template <class Args> __device__ __forceinline__ bool treeq_row_live(const Args &A, uint32_t r, uint32_t expect) {
+    if (r >= A.nrows) return false;                                        // (ghost instances live beyond the entity rows; they are not walked, and not read if they were)
+    const uint32_t fl = A.row_flags[r], rc = A.row_cell[r];
+    return !(fl & (F_DEAD | F_PHANTOM)) && rc == expect && (fl & A.need) == A.need && !(fl & A.forbid);
+}
+// does the row belong to the rule for this query?
+template <class Shape> __device__ __forceinline__ bool treeq_row_hit(const typename Shape::Args &A, const Shape &P, uint32_t r, uint32_t expect, uint32_t query, typename Shape::Rec &rec) {
+    return treeq_row_live(A, r, expect) && P.test(A.row_aabb[r], &A.row_id[r], query, rec);
+}
+
+// one wave walks rows[begin .. begin + cnt): one lane per row, ballot + mbcnt compaction into the workgroup's staging buffer
+template <class Shape> __device__ __forceinline__ void treeq_walk_wave(const typename Shape::Args &A, TreeqShared<Shape> &S, const Shape &P, uint32_t query, uint32_t begin, uint32_t cnt, uint32_t expect) {
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t base = 0; base < cnt; base += 64u) {                     // (wave-uniform trip count)
+        const uint32_t k = base + lane;
+        typename Shape::Rec rec{};
+        bool hit = false;
+        if (k < cnt) hit = treeq_row_hit(A, P, A.rows[begin + k], expect, query, rec);
+        const uint64_t mask = __ballot(hit);
+        if (!mask) continue;
+        uint32_t pos = 0;
+        if (lane == 0u) pos = atomicAdd(&S.n_hits, (uint32_t)__popcll(mask));
+        pos = __shfl(pos, 0) + treeq_mbcnt(mask);
+        if (hit && pos < BOXQ_HITBUF) S.hits[pos] = rec;
+        const uint64_t over = __ballot(hit && pos >= BOXQ_HITBUF);        // the staging buffer is full: this wave's remainder goes out directly
+        if (over) {
+            uint32_t g = 0;
+            if (lane == 0u) g = atomicAdd(&A.hdr->count, (uint32_t)__popcll(over));
+            g = __shfl(g, 0) + treeq_mbcnt(over);
+            if (hit && pos >= BOXQ_HITBUF) Shape::store(A, g, rec);
+        }
+    }
+}
+
+template <class Shape> __device__ __forceinline__ void treeq_unique_part(const typename Shape::Args &A, TreeqShared<Shape> &S) {
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, query = blockIdx.x;
+    const typename Shape::Query &Q = A.q[query];
+    const uint32_t nlev = A.max_level + 1u;                                // an entity longer than half the outline sits at level max_level
+    Shape::stage(S.own, Q, tid);
+    if (tid < nlev) {
+        const uint32_t len = A.atomic << tid;
+        for (uint32_t a = 0; a < 3u; a++) {
+            uint32_t lo, hi; box_level_range(Q.umin[a], Q.umax[a], (Q.flags >> a) & 1u, len, &lo, &hi);
+            S.lo[a][tid] = lo; S.ext[a][tid] = hi - lo + 1u;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t sum = 0;
+        for (uint32_t l = 0; l < nlev; l++) { S.prefix[l] = sum; sum += S.ext[0][l] * S.ext[1][l] * S.ext[2][l]; }      // (<= RE_BOX_QUERY_MAX_CELLS: the host refused the query otherwise)
+        S.prefix[nlev] = sum;
+    }
+    __syncthreads();
+    const uint32_t total = S.prefix[nlev];
+    const Shape P = S.own;
+    for (uint32_t base = 0; base < total; base += BOXQ_QUEUE) {            // rounds of 1024 candidate cells
+        for (uint32_t j = 0; j < BOXQ_PROBES; j++) {
+            const uint32_t g = base + j * BOXQ_THREADS + tid;
+            if (g >= total) break;
+            uint32_t l = 0;
+            while (g >= S.prefix[l + 1u]) l++;                             // (l < nlev: g < prefix[nlev])
+            const uint32_t idx = g - S.prefix[l], nx = S.ext[0][l], ny = S.ext[1][l];
+            const uint32_t ix = idx % nx, rest = idx / nx, iy = rest % ny, iz = rest / ny;
+            const uint32_t cx = S.lo[0][l] + ix, cy = S.lo[1][l] + iy, cz = S.lo[2][l] + iz, len = A.atomic << l;
+            const uint32_t c0[3] = { cx * len, cy * len, cz * len }, c1[3] = { cx * len + len, cy * len + len, cz * len + len };
+            if (P.misses(Shape::cell_box(A, c0, c1))) continue;
+            const uint64_t key = pack_key(l, cx, cz, cy);
+            const int32_t slot = rb_find(A.T, A.cell_key, key);
+            if (slot >= 0 && A.cell_nl[slot] + A.cell_ns[slot] != 0u) S.queue[atomicAdd(&S.n_queue, 1u)] = (uint32_t)slot;
+        }
+        __syncthreads();
+        const uint32_t nq = S.n_queue;
+        for (uint32_t e = wave; e < nq; e += BOXQ_THREADS / 64u) {          // one wave per hit section: active rows, then static rows; the ghost tail is not walked
+            const uint32_t slot = S.queue[e];
+            treeq_walk_wave(A, S, P, query, A.cell_begin[slot], A.cell_nl[slot] + A.cell_ns[slot], slot);
+        }
+        treeq_flush(A, S);
+        if (tid == 0) S.n_queue = 0u;
+        __syncthreads();
+    }
+}
+
+// the cell of one linked key against one query: is the cell inside the query's range of the key's level?  Integer form of box_level_range:
+// x <= umax / len  <=>  x * len <= umax;   x >= lo  <=>  (x + 1) * len + whole > umin  (lo = umin / len, one less when umin is a whole multiple of len)
+__device__ __forceinline__ bool treeq_cell_in_range(uint32_t c0, uint32_t c1, uint32_t umin, uint32_t umax, uint32_t whole) {
+    return c0 <= umax && c1 + whole > umin;
+}
+__device__ __forceinline__ bool treeq_cells_in_range(const uint32_t *c0, const uint32_t *c1, const uint32_t *t) {      // t: the head of a tile entry
+    const uint32_t fl = t[6];
+    return treeq_cell_in_range(c0[0], c1[0], t[0], t[3], fl & 1u) && treeq_cell_in_range(c0[1], c1[1], t[1], t[4], (fl >> 1) & 1u) &&
+           treeq_cell_in_range(c0[2], c1[2], t[2], t[5], (fl >> 2) & 1u);
+}
+
+template <class Shape> __device__ __forceinline__ void treeq_shared_part(const typename Shape::Args &A, TreeqShared<Shape> &S) {
+    const uint32_t tid = threadIdx.x, sb = blockIdx.x - A.n;
+    const uint32_t chunk = sb % A.n_sh_chunks, q0 = (sb / A.n_sh_chunks) * BOXQ_TILE;
+    const uint32_t nq = A.n - q0 < BOXQ_TILE ? A.n - q0 : BOXQ_TILE;
+    uint32_t *tile = S.queue;
+    if (tid < nq) {
+        const typename Shape::Query &Q = A.q[q0 + tid];
+        uint32_t *t = tile + tid * Shape::TILE_WORDS;
+        for (uint32_t a = 0; a < 3u; a++) { t[a] = Q.umin[a]; t[3u + a] = Q.umax[a]; }
+        t[6] = Q.flags;
+        Shape::to_tile(Q, t + TREEQ_TILE_HEAD);
+    }
+    __syncthreads();
+    const uint32_t s = chunk * BOXQ_THREADS + tid;
+    const uint32_t nk = s < A.nsh ? A.sh_nk[s] : 0u;                        // holes: nk == 0
+    const uint32_t cnt = nk ? A.sh_nact[s] + A.sh_nstat[s] : 0u;
+    if (cnt) {
+        uint64_t keys[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) keys[k] = A.sh_keys[(size_t)s * 8u + k];
+        // the bounding cell box of the linked keys, in world units: most (query, shared section) pairs end at its integer test, the rest at the shape's prune
+        uint32_t b0[3] = { 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu }, b1[3] = { 0u, 0u, 0u };
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+            if ((uint32_t)k < nk) {
+                const uint32_t len = A.atomic << key_level(keys[k]);
+                const uint32_t c[3] = { key_x(keys[k]) * len, key_y(keys[k]) * len, key_z(keys[k]) * len };
+#pragma unroll
+                for (int a = 0; a < 3; a++) { b0[a] = c[a] < b0[a] ? c[a] : b0[a]; b1[a] = c[a] + len > b1[a] ? c[a] + len : b1[a]; }
+            }
+        const typename Shape::CellBox bound = Shape::cell_box(A, b0, b1);
+        // the first member (most shared sections hold one entity) is fetched ONCE, in front of the loop over the queries: a section of a high level is a
+        // candidate of every query, and a lane that gathered its row per query would spend four dependent round trips on each
+        const uint32_t begin = A.sh_begin[s], expect = ROW_CELL_SHARED | s;
+        const uint32_t r0 = A.rows[begin];
+        const bool live0 = treeq_row_live(A, r0, expect);
+        Aabb a0 = {}; uint32_t id0 = 0;
+        if (r0 < A.nrows) { a0 = A.row_aabb[r0]; id0 = A.row_id[r0]; }
+        for (uint32_t i = 0; i < nq; i++) {
+            const uint32_t *t = tile + i * Shape::TILE_WORDS;
+            if (!treeq_cells_in_range(b0, b1, t)) continue;
+            bool any = false;
+#pragma unroll
+            for (int k = 0; k < 8; k++)
+                if ((uint32_t)k < nk) {
+                    const uint32_t len = A.atomic << key_level(keys[k]);
+                    const uint32_t c0[3] = { key_x(keys[k]) * len, key_y(keys[k]) * len, key_z(keys[k]) * len }, c1[3] = { c0[0] + len, c0[1] + len, c0[2] + len };
+                    any = any || treeq_cells_in_range(c0, c1, t);
+                }
+            if (!any) continue;
+            const Shape P = Shape::from_tile(t + TREEQ_TILE_HEAD);
+            if (P.misses(bound)) continue;
+            // walked ONCE for this query, however many of its linked keys lie in the range
+            for (uint32_t m = 0; m < cnt; m++) {
+                typename Shape::Rec rec{};
+                if (m == 0u ? !(live0 && P.test(a0, &id0, q0 + i, rec)) : !treeq_row_hit(A, P, A.rows[begin + m], expect, q0 + i, rec)) continue;
+                const uint32_t pos = atomicAdd(&S.n_hits, 1u);
+                if (pos < BOXQ_HITBUF) S.hits[pos] = rec;
+                else Shape::store(A, atomicAdd(&A.hdr->count, 1u), rec);
+            }
+        }
+    }
+    treeq_flush(A, S);
+}
+
+// Grid: workgroups [0, n) take one query each through the unique sections; the workgroups behind them take (256 shared sections) x (256 queries) each.
+// 256 threads, 64-wide waves, no recursion; every loop is bounded (candidate cells by the host's cap, rb_find's probe by an empty slot of an overlay that is
+// never full and a binary search, the row walks by the sections' counts).
+// Publication: write-through records, every wave waits for its own stores, then the workgroup signs off (list_sign_off, re_kernels.h).
+template <class Shape> __device__ __forceinline__ void treeq_kernel(const typename Shape::Args &A, TreeqShared<Shape> &S) {
+    if (threadIdx.x == 0) { S.n_hits = 0u; S.n_queue = 0u; }
+    __syncthreads();
+    if (blockIdx.x < A.n) treeq_unique_part(A, S); else treeq_shared_part(A, S);
+    wait_own_stores();
+    __syncthreads();                                                          // every wave's records have left; the count atomics have returned
+    if (threadIdx.x == 0) list_sign_off(A.hdr, A.h_pub, A.seq);
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(BOXQ_THREADS) void k_box_query(BoxQueryArgs A) { __shared__ TreeqShared<BoxShape> S; treeq_kernel(A, S); }
+__global__ __launch_bounds__(BOXQ_THREADS) void k_segment_query(SegQueryArgs A) { __shared__ TreeqShared<SegShape> S; treeq_kernel(A, S); }
+
+}  // namespace re

@@ -352,13 +352,7 @@ class Pipeline:
         """LogicFlow::handle_collisions (flows/logic_flow.rs:452-651) of the frame, between cull_and_pack and tick: array [n, 2] of
         the (this_entity, other_entity) arguments of every collision-logic invocation, in no particular order.  capacity=None: two
         calls, the first asks for the total; capacity=0: one call without a buffer, which returns the total alone"""
-        n = C.c_uint32()
-        if capacity is None:
-            self._check(self._L.re_collide(self._h, 0, None, 0, C.byref(n)), "re_collide")
-            capacity = n.value
-        pairs = np.zeros((max(capacity, 1), 2), np.uint32)
-        self._check(self._L.re_collide(self._h, 0, pairs.ctypes.data if capacity else None, capacity, C.byref(n)), "re_collide")
-        return pairs[:min(n.value, capacity)].copy(), n.value
+        return self._record_list(self._L.re_collide, (0,), "re_collide", capacity, np.uint32, row=(2,), null_when_empty=True)
 
     # -- entity logic: LogicFlow::update_logic (flows/logic_flow.rs:245) up to the callbacks ---------------
     def set_entity_types(self, ids, type_identifiers):
@@ -392,12 +386,17 @@ class Pipeline:
     def logic_calls(self, capacity=None):
         """the frame's entity-logic call list, between cull_and_pack (and collide) and tick: (records, n_total) with records a LOGIC_CALL_DT array
         (entity_id, logic_index into the table, which, times) in no particular order"""
+        return self._record_list(self._L.re_logic_list, (0,), "re_logic_list", capacity, _capi.LOGIC_CALL_DT)
+
+    def _record_list(self, fn, lead, name, capacity, dtype, row=(), null_when_empty=False):
+        """the two-call idiom of the record-list entry points fn(ctx, *lead, records, capacity, &n_total): capacity=None asks for the total first; then one
+        call into max(capacity, 1) records of dtype (each of shape row).  Returns (records[:min(n_total, capacity)], n_total).  null_when_empty: capacity 0 passes no buffer at all."""
         n = C.c_uint32()
         if capacity is None:
-            self._check(self._L.re_logic_list(self._h, 0, None, 0, C.byref(n)), "re_logic_list")
+            self._check(fn(self._h, *lead, None, 0, C.byref(n)), name)
             capacity = n.value
-        rec = np.zeros(max(capacity, 1), _capi.LOGIC_CALL_DT)
-        self._check(self._L.re_logic_list(self._h, 0, rec.ctypes.data, capacity, C.byref(n)), "re_logic_list")
+        rec = np.zeros((max(capacity, 1),) + row, dtype)
+        self._check(fn(self._h, *lead, None if null_when_empty and not capacity else rec.ctypes.data, capacity, C.byref(n)), name)
         return rec[:min(n.value, capacity)].copy(), n.value
 
     # -- tree queries: what the logic callbacks get instead of &BoundingBoxTree ------------------------------
@@ -406,13 +405,7 @@ class Pipeline:
         array (query, entity_id) in no particular order; need_flags / forbid_flags filter by the F_* bits of the entity.  Valid at any point between calls."""
         boxes = np.ascontiguousarray(boxes, np.float32).reshape(-1, 6)
         args = _capi.BoxQueryArgs(int(need_flags), int(forbid_flags)) if (need_flags or forbid_flags) else None
-        n = C.c_uint32()
-        if capacity is None:
-            self._check(self._L.re_query_boxes(self._h, boxes.ctypes.data, len(boxes), args, None, 0, C.byref(n)), "re_query_boxes")
-            capacity = n.value
-        hits = np.zeros(max(capacity, 1), _capi.BOX_HIT_DT)
-        self._check(self._L.re_query_boxes(self._h, boxes.ctypes.data, len(boxes), args, hits.ctypes.data, capacity, C.byref(n)), "re_query_boxes")
-        return hits[:min(n.value, capacity)].copy(), n.value
+        return self._record_list(self._L.re_query_boxes, (boxes.ctypes.data, len(boxes), args), "re_query_boxes", capacity, _capi.BOX_HIT_DT)
 
     def find_entities_along_segments(self, segments, exclude=None, need_flags=0, forbid_flags=0, capacity=None):
         """the entities whose StaticAABB each segment of a batch meets ([n, 6]: p0 xyz, p1 xyz, or a SEGMENT_DT array): (hits, n_total) with hits a
@@ -427,13 +420,7 @@ class Pipeline:
             seg["p0"], seg["p1"] = pts[:, 0:3], pts[:, 3:6]
             seg["exclude_entity"] = _capi.SEGMENT_NO_ENTITY if exclude is None else np.asarray(exclude, np.uint32)
         args = _capi.BoxQueryArgs(int(need_flags), int(forbid_flags)) if (need_flags or forbid_flags) else None
-        n = C.c_uint32()
-        if capacity is None:
-            self._check(self._L.re_query_segments(self._h, seg.ctypes.data, len(seg), args, None, 0, C.byref(n)), "re_query_segments")
-            capacity = n.value
-        hits = np.zeros(max(capacity, 1), _capi.SEGMENT_HIT_DT)
-        self._check(self._L.re_query_segments(self._h, seg.ctypes.data, len(seg), args, hits.ctypes.data, capacity, C.byref(n)), "re_query_segments")
-        return hits[:min(n.value, capacity)].copy(), n.value
+        return self._record_list(self._L.re_query_segments, (seg.ctypes.data, len(seg), args), "re_query_segments", capacity, _capi.SEGMENT_HIT_DT)
 
     # -- multi-GPU exchange (RCCL behind the C ABI) ---------------------------------------------------
     @staticmethod

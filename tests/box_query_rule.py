@@ -136,6 +136,49 @@ def probe_queries(atomic=64, outline=16384):
     return q, [(0, 0), (0, 1), (0, 2), (0, 4), (1, 1), (1, 2), (2, 3)]
 
 
+N_CROWD = 1100                   # more than the 1024 records a query workgroup stages between two flushes (BOXQ_HITBUF)
+
+
+def overflow_world(atomic=64):
+    """probe_world and two crowds of N_CROWD entities each (coordinates in units of atomic / 64):
+    ids 100 .. 1199:  copies of entity 5, [100, 128]^3  -> all in the unique section (1, 1, 1) with it: ONE WAVE walks more rows that hit than the
+                      workgroup stages (the overflow of the row walk)
+    ids 5000 .. 6099: [639, 641]^3, straddling a section corner -> all in one shared section of 8 links: ONE LANE emits more records than the workgroup
+                      stages (the overflow of the shared part)"""
+    import render_engine_amd as R
+    s = np.float32(atomic) / np.float32(64.0)
+    base = probe_world(atomic)
+    crowd = np.zeros(2 * N_CROWD, R.ENTITY_DT)
+    crowd[:] = base[5]
+    crowd["id"] = np.concatenate([100 + np.arange(N_CROWD), 5000 + np.arange(N_CROWD)])
+    crowd["original"][N_CROWD:] = np.array([639, 641] * 3, np.float32) * s
+    return np.concatenate([base, crowd])
+
+
+def assert_overflow_placement(w):
+    """the oracle's placement of overflow_world that the GPU tests of the overflow paths rest on: one key set for the first crowd, one shared section of
+    8 links with N_CROWD members for the second"""
+    kind5, keys5 = w.lookup(5)
+    assert kind5 == 1 and keys5 == [ro.pack_key(0, 1, 1, 1)]
+    assert {(w.lookup(e)[0], tuple(w.lookup(e)[1])) for e in range(100, 100 + N_CROWD)} == {(1, tuple(keys5))}
+    kind, keys = w.lookup(5000)
+    assert kind == 2 and len(keys) == 8
+    assert all(w.lookup(e) == (kind, keys) for e in range(5000, 5000 + N_CROWD))
+    mine = [sh for sh in w.shared_sections() if sorted(sh["keys"]) == sorted(keys)]
+    assert len(mine) == 1 and len(mine[0]["active"]) + len(mine[0]["static"]) == N_CROWD
+    assert sorted(int(e) for e in np.concatenate([mine[0]["active"], mine[0]["static"]])) == list(range(5000, 5000 + N_CROWD))
+
+
+def overflow_queries(atomic=64):
+    """(boxes [2, 6], p0 [2, 3], p1 [2, 3]): query 0 over the first crowd of overflow_world (and entity 5: N_CROWD + 1 hits), query 1 over the second
+    (N_CROWD hits), as boxes and as segments along x through the middle of each crowd"""
+    s = np.float32(atomic) / np.float32(64.0)
+    boxes = np.array([[90, 130] * 3, [630, 650] * 3], np.float32) * s
+    p0 = np.array([[90, 114, 114], [630, 640, 640]], np.float32) * s
+    p1 = np.array([[130, 114, 114], [650, 640, 640]], np.float32) * s
+    return boxes, p0, p1
+
+
 N_BORDER = 12
 
 

@@ -7,7 +7,7 @@ import pytest
 
 import oracle as ro
 from helpers import to_oracle, oracle_camera
-from box_query_rule import box_hits, probe_world, probe_push_out, probe_queries, query_world, draw_boxes
+from box_query_rule import box_hits, probe_world, probe_push_out, probe_queries, query_world, draw_boxes, overflow_world, overflow_queries
 from test_gpu_parity import build_pair, check_frame, random_changes, assert_clean_publication
 from test_logic_rule import camera_draw
 
@@ -139,6 +139,29 @@ def test_known_answers_on_the_device(R, atomic):
     # one box over all of them: everything the tree holds there, once
     q = np.array([[0, 1500 * s] * 3], np.float32)
     assert ask(p, q)[0] == box_hits(w, ids, q) == [(0, e) for e in (0, 1, 2, 4, 5, 6, 7, 8)]
+    assert_clean_publication(p)
+    p.close(); w.close()
+
+
+@pytest.mark.parametrize("atomic", [64, 16])
+def test_staging_overflow(R, atomic):
+    """more records in one workgroup than it stages (BOXQ_HITBUF = 1024; tests/test_box_query_rule.py holds the precondition): box 0 makes one wave walk
+    1101 hit rows of one unique section (the overflow of the row walk), box 1 makes one lane emit the 1100 members of one shared section (the overflow of
+    the shared part)"""
+    ents = overflow_world(atomic)
+    p, w = build_pair(R, ents, atomic=atomic)
+    ids = [int(i) for i in ents["id"]]
+    boxes, _, _ = overflow_queries(atomic)
+    want = box_hits(w, ids, boxes)
+    assert len(want) == 2201
+    for _ in range(2):                                                 # the same call again: the header was left zero
+        got, n_total = ask(p, boxes)
+        assert got == want and n_total == len(want)
+    hits, n_total = p.find_entities_in_boxes(boxes, capacity=0)
+    assert n_total == len(want) and len(hits) == 0
+    hits, n_total = p.find_entities_in_boxes(boxes, capacity=1050)     # above the stage, below the total
+    assert n_total == len(want) and len(hits) == 1050 and len(set(pairs_of(hits))) == 1050 and set(pairs_of(hits)) <= set(want)
+    assert ask(p, boxes) == (want, len(want))
     assert_clean_publication(p)
     p.close(); w.close()
 

@@ -7,7 +7,7 @@ import pytest
 import oracle as ro
 from helpers import to_oracle, oracle_camera
 from box_query_rule import (MAX_CELLS, box_hits, query_cell_ranges, candidate_cell_count, key_in_ranges, probe_world, probe_push_out, probe_queries,
-                            query_world, draw_boxes)
+                            query_world, draw_boxes, N_CROWD, overflow_world, overflow_queries, assert_overflow_placement)
 from test_logic_rule import camera_draw
 
 WORLDS = [(2500, 5, 160.0, 64), (1500, 13, 150.0, 16)]      # n, seed, spread, atomic: the worlds of test_logic_gpu.py
@@ -69,6 +69,23 @@ def test_every_hit_has_a_key_in_the_cell_ranges(n, seed, spread, atomic):
         for _ in range(3):
             w.tick(oracle_camera(camera_draw(R, rng, spread)), 0.05)
     assert pairs >= 200 and through_shared >= 20 and minus_one_only >= 5, (pairs, through_shared, minus_one_only)
+    w.close()
+
+
+@pytest.mark.parametrize("atomic", [64, 16])
+def test_overflow_world_exceeds_the_staging_buffer(atomic):
+    """the precondition of the GPU test of the overflow paths (test_box_query_gpu.py): the placement of overflow_world, and both boxes return more
+    records than a workgroup stages"""
+    ents = overflow_world(atomic)
+    w = ro.World(16384, atomic)
+    assert w.register(to_oracle(ents)) == 0
+    assert_overflow_placement(w)
+    boxes, _, _ = overflow_queries(atomic)
+    got = box_hits(w, [int(i) for i in ents["id"]], boxes)
+    per_query = [sum(1 for i, _ in got if i == q) for q in range(2)]
+    assert per_query == [N_CROWD + 1, N_CROWD] == [1101, 1100]
+    assert min(per_query) > 1024                                                 # BOXQ_HITBUF (re_kernels.h)
+    assert sorted(e for i, e in got if i == 0) == [5] + list(range(100, 100 + N_CROWD)) and sorted(e for i, e in got if i == 1) == list(range(5000, 5000 + N_CROWD))
     w.close()
 
 

@@ -20,7 +20,7 @@ def test_symbol_is_exported_and_declared():
                      r"\s*re_segment_hit\s*\*hits,\s*uint32_t\s+capacity,\s*uint32_t\s*\*n_total\s*\)\s*;", header)
     assert "#define RE_SEGMENT_NO_ENTITY 0xFFFFFFFFu" in header
     assert L.re_abi_version() == 3                                   # additions only
-    assert "re_segquery.hip" in __import__("render_engine_amd.build", fromlist=["SOURCES"]).SOURCES
+    assert "re_treequery.hip" in __import__("render_engine_amd.build", fromlist=["SOURCES"]).SOURCES
 
 
 def test_record_sizes():

@@ -8,7 +8,7 @@ import pytest
 
 import oracle as ro
 from helpers import to_oracle, oracle_camera
-from box_query_rule import probe_world, query_world
+from box_query_rule import probe_world, query_world, overflow_world, overflow_queries
 from segment_rule import NO_ENTITY, segment_hits, records_of, first_hits_brute, draw_segments
 from test_segment_rule import known_world, known_segments
 from box_query_rule import probe_push_out
@@ -135,6 +135,30 @@ def test_known_answers_on_the_device(R, atomic):
     ch = np.zeros(1, R.CHANGE_DT); ch[0] = (L.CHANGE_ADD_ENTITY, 8, 0, 0, (0, 0, 0, 0))
     w.apply_changes(ch.view(ro.CHANGE_DT), added=to_oracle(add)); p.apply_changes(ch, added=add)
     assert ask(p, a, b)[0] == [(1, 8, F32(0.25).view(np.uint32), F32(0.75).view(np.uint32))] == segment_hits(w, ids, a, b)
+    assert_clean_publication(p)
+    p.close(); w.close()
+
+
+@pytest.mark.parametrize("atomic", [64, 16])
+def test_staging_overflow(R, atomic):
+    """more records in one workgroup than it stages (BOXQ_HITBUF = 1024; tests/test_segment_rule.py holds the precondition): segment 0 makes one wave
+    walk 1101 hit rows of one unique section (the overflow of the row walk), segment 1 makes one lane emit the 1100 members of one shared section (the
+    overflow of the shared part); t_enter and t_exit bit for bit"""
+    ents = overflow_world(atomic)
+    p, w = build_pair(R, ents, atomic=atomic)
+    ids = [int(i) for i in ents["id"]]
+    _, p0, p1 = overflow_queries(atomic)
+    both = np.concatenate([p0, p1], axis=1)
+    want = segment_hits(w, ids, p0, p1)
+    assert len(want) == 2201
+    for _ in range(2):                                                 # the same call again: the header was left zero
+        got, n_total = ask(p, p0, p1)
+        assert got == want and n_total == len(want), describe(got, want)
+    hits, n_total = p.find_entities_along_segments(both, capacity=0)
+    assert n_total == len(want) and len(hits) == 0
+    hits, n_total = p.find_entities_along_segments(both, capacity=1050)      # above the stage, below the total
+    assert n_total == len(want) and len(hits) == 1050 and len(set(records_of(hits))) == 1050 and set(records_of(hits)) <= set(want)
+    assert ask(p, p0, p1) == (want, len(want))
     assert_clean_publication(p)
     p.close(); w.close()
 

@@ -6,7 +6,7 @@ import pytest
 
 import oracle as ro
 from helpers import to_oracle, oracle_camera
-from box_query_rule import MAX_CELLS, query_cell_ranges, key_in_ranges, probe_world, probe_push_out, query_world
+from box_query_rule import MAX_CELLS, query_cell_ranges, key_in_ranges, probe_world, probe_push_out, query_world, N_CROWD, overflow_world, overflow_queries, assert_overflow_placement
 from segment_rule import (F32, NO_ENTITY, SEGMENT_HIT_DT, segment_hits, first_hits_brute, direction, bounding_box, segment_cell_count, key_cells, prune_passes,
                           pruned_fraction, draw_segments, margin)
 from test_logic_rule import camera_draw
@@ -147,6 +147,23 @@ def test_every_hit_is_reached_by_the_walk(n, seed, spread, atomic):
     print(dict(pairs=pairs, through_shared=through_shared, touch=touch, special=special, cells=cells, kept=kept))
     assert pairs >= 500 and through_shared >= 100 and touch >= 10 and special >= 5, (pairs, through_shared, touch, special)
     assert 2 * kept <= cells, (kept, cells)
+    w.close()
+
+
+@pytest.mark.parametrize("atomic", [64, 16])
+def test_overflow_world_exceeds_the_staging_buffer(atomic):
+    """the precondition of the GPU test of the overflow paths (test_segment_query_gpu.py): the placement of overflow_world, and both segments return more
+    records than a workgroup stages"""
+    ents = overflow_world(atomic)
+    w = ro.World(16384, atomic)
+    assert w.register(to_oracle(ents)) == 0
+    assert_overflow_placement(w)
+    _, p0, p1 = overflow_queries(atomic)
+    got = segment_hits(w, [int(i) for i in ents["id"]], p0, p1)
+    per_query = [sum(1 for r in got if r[0] == q) for q in range(2)]
+    assert per_query == [N_CROWD + 1, N_CROWD] == [1101, 1100]
+    assert min(per_query) > 1024                                                 # BOXQ_HITBUF (re_kernels.h)
+    assert sorted(r[1] for r in got if r[0] == 0) == [5] + list(range(100, 100 + N_CROWD)) and sorted(r[1] for r in got if r[0] == 1) == list(range(5000, 5000 + N_CROWD))
     w.close()
 
 
