@@ -529,6 +529,8 @@ int re_debug_get_plan_stats(re_ctx *ctx, uint32_t *n_plan_frames, uint32_t *last
 /* bytes of DEVICE memory of the ctx (a packed or gathered buffer) into host memory, ordered behind the work on the ctx's stream -- for hosts that hold no HIP
  * runtime of their own, or a different one (a process may carry a second ROCm stack: a pointer of this library means nothing to that one) */
 int re_debug_copy_to_host(re_ctx *ctx, const void *d_src, void *dst, uint64_t bytes);
+/* blocks of device and pinned host memory the contexts of this process hold at the moment (blocks, not bytes): back at its earlier value once a context is destroyed */
+uint64_t re_debug_live_allocations(void);
 /* the HIP stream of the ctx (hipStream_t as void*) so callers can order their own work after it */
 void *re_get_stream(re_ctx *ctx);
 

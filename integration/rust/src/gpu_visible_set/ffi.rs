@@ -104,6 +104,7 @@ extern "C" {
     pub fn re_export_entities(ctx: *mut ReCtx, entity_ids: *const u32, n: u32, out: *mut ReEntityState) -> c_int;
     pub fn re_get_stats(ctx: *mut ReCtx, out: *mut ReStats) -> c_int;
     pub fn re_debug_copy_to_host(ctx: *mut ReCtx, d_src: *const c_void, dst: *mut c_void, bytes: u64) -> c_int;
+    pub fn re_debug_live_allocations() -> u64;
     // introspection / profiling
     pub fn re_debug_get_sections(ctx: *mut ReCtx, capacity: u32, keys: *mut u64, tight_aabb6: *mut f32, n_local: *mut u32, n_static: *mut u32, is_static_section: *mut u8, n: *mut u32) -> c_int;
     pub fn re_debug_get_shared_sections(ctx: *mut ReCtx, capacity: u32, keys: *mut u64, n_keys: *mut u8, aabb6: *mut f32, n_active: *mut u32, n_static: *mut u32,

@@ -190,7 +190,7 @@ EXPORTS = ["re_create", "re_destroy", "re_last_error", "re_abi_version", "re_upl
            "re_apply_changes", "re_apply_changes_ex", "re_add_entities", "re_set_shard_range", "re_list_migrants", "re_export_entities", "re_collide",
            "re_set_entity_types", "re_get_entity_type", "re_set_entity_logic", "re_logic_list", "re_query_boxes", "re_query_segments", "re_wait", "re_run_frames", "re_comm_unique_id", "re_comm_init", "re_comm_adopt", "re_comm_destroy", "re_allgather_visible", "re_gather_wait", "re_copy_visible", "re_set_output_buffers", "re_set_output_count", "re_read_component", "re_set_light_information", "re_ecs_bitset", "re_ecs_query", "re_visible_lights", "re_section_keys", "re_get_out_of_bounds", "re_get_stats",
            "re_debug_get_sections", "re_debug_get_shared_sections", "re_debug_get_visible_sections", "re_debug_copy_to_host", "re_get_timings", "re_get_stream",
-           "re_timing_begin", "re_timing_collect", "re_get_last_candidates", "re_debug_get_plan_stats",
+           "re_timing_begin", "re_timing_collect", "re_get_last_candidates", "re_debug_get_plan_stats", "re_debug_live_allocations",
            "re_lighting_create", "re_lighting_destroy", "re_lighting_last_error", "re_lighting_upload_gbuffer", "re_lighting_set_lights",
            "re_lighting_run", "re_lighting_read", "re_lighting_read_pixels", "re_lighting_set_lights_from_world",
            "re_shadow_create", "re_shadow_destroy", "re_shadow_last_error", "re_shadow_step", "re_shadow_uploads", "re_shadow_get_stats",
@@ -270,6 +270,7 @@ def load():
     L.re_debug_get_plan_stats.restype = C.c_int; L.re_debug_get_plan_stats.argtypes = [vp, _u32p, _u32p, _u32p]
     L.re_get_timings.restype = C.c_int; L.re_get_timings.argtypes = [vp, _fp, _fp, _fp]
     L.re_debug_copy_to_host.restype = C.c_int; L.re_debug_copy_to_host.argtypes = [vp, vp, vp, C.c_uint64]
+    L.re_debug_live_allocations.restype = C.c_uint64; L.re_debug_live_allocations.argtypes = []
     L.re_get_stream.restype = vp; L.re_get_stream.argtypes = [vp]
     L.re_set_output_count.restype = C.c_int; L.re_set_output_count.argtypes = [vp, vp]
     L.re_timing_begin.restype = C.c_int; L.re_timing_begin.argtypes = [vp, C.c_uint32, C.c_uint32]

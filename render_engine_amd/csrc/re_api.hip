@@ -23,6 +23,7 @@
 #include "re_guard.h"
 #include "re_kernels.h"
 #include "re_math.h"
+#include "re_own.h"
 #include "re_wait.h"
 #include "re_world_lights.h"
 
@@ -31,18 +32,6 @@ using namespace re;
 static thread_local std::string g_create_error;
 
 namespace {
-
-template <typename T> struct DevBuf {
-    T *p = nullptr; size_t n = 0;
-    hipError_t alloc(size_t count, uint64_t *acct) {
-        release(acct);
-        if (count == 0) count = 1;
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), count * sizeof(T));
-        if (e == hipSuccess) { n = count; if (acct) *acct += count * sizeof(T); } else p = nullptr;
-        return e;
-    }
-    void release(uint64_t *acct) { if (p) { (void)hipFree(p); if (acct) *acct -= n * sizeof(T); } p = nullptr; n = 0; }
-};
 
 struct GroupKey { uint32_t model, rs, sort; bool operator==(const GroupKey &o) const { return model == o.model && rs == o.rs && sort == o.sort; } };
 struct GroupKeyHash { size_t operator()(const GroupKey &k) const { return (size_t)k.model * 0x9E3779B97F4A7C15ull ^ ((size_t)k.rs << 32) ^ ((size_t)k.sort << 20); } };
@@ -81,30 +70,42 @@ static void comm_release(re_ctx *c);
 // The host end of a record-list flow: the device header its kernel's workgroups sign off on (list_sign_off, re_kernels.h), the mapped
 // block the last of them publishes count, seal and sequence number into, and the sequence numbers of the calls.  Both live from the first call to re_destroy.
 struct ListChannel {
-    DevBuf<LogicHeader> hdr; LogicPublished *h_pub = nullptr, *d_pub = nullptr; uint32_t calls = 0;      // (d_pub: the device's address of the mapped block)
+    DevBuf<LogicHeader> hdr; Pinned pub; LogicPublished *h_pub = nullptr, *d_pub = nullptr; uint32_t calls = 0;      // (h_pub, d_pub: the host's and the device's address of the mapped block)
     int open(re_ctx *c);                                   // at the first call: the header and the mapped block, both zero
     uint32_t next_seq() { return ++calls; }
     int wait(re_ctx *c, uint32_t seq, uint32_t *n);       // completion of call `seq`: polls the sequence number the last workgroup publishes (a stream synchronise costs tens of microseconds)
-    void close() { if (h_pub) { (void)hipHostFree(h_pub); h_pub = d_pub = nullptr; } hdr.release(nullptr); }
 };
 // One kind of tree query (re_query_boxes, re_query_segments): the batch travels from two pinned buffers that alternate by call into one device array; records
 // come back through d_out; header block, mapped block and sequence numbers of its own.  Allocated lazily, kept across uploads.
 template <class Query> struct QueryFlow {
-    Query *h_q[2] = {}; size_t h_cap[2] = {}; uint32_t k = 0; DevBuf<Query> d_q; DevBuf<unsigned long long> d_out; ListChannel ch;
-    void release() {
-        ch.close(); d_q.release(nullptr); d_out.release(nullptr);
-        for (int i = 0; i < 2; i++) if (h_q[i]) { (void)hipHostFree(h_q[i]); h_q[i] = nullptr; h_cap[i] = 0; }
+    Pinned h_q[2]; uint32_t k = 0; DevBuf<Query> d_q; DevBuf<unsigned long long> d_out; ListChannel ch;
+};
+// Everything the kernels publish to the polling host thread lives in ONE block of mapped, coherent pinned host memory per frame lane
+// (hipHostMallocMapped | hipHostMallocCoherent): the frame result at 0, the speculation word at 128, the tick counters at 256, the
+// InstanceRange table from 8192 on.  (Round 1 used four separate mapped blocks; what made its group table arrive after
+// the "frame done" word was not the number of blocks but the plain store of that word -- see publish_to_host in re_kernels.h.)
+constexpr size_t HB_RES = 0, HB_SPEC = 128, HB_TICK = 256, HB_RANGES = 8192;
+static_assert(sizeof(HostResult) <= HB_SPEC && sizeof(SpecState) <= HB_TICK - HB_SPEC && HB_TICK + sizeof(TickHeader) <= HB_RANGES, "host block layout");
+// One lane's block with its typed views (d_* = the device's view).  The second lane uses the frame result and the group table of its block only.
+struct HostBlock {
+    Pinned h_block;
+    HostResult *h_res = nullptr, *d_hres = nullptr; InstanceRange *h_ranges = nullptr, *d_hranges = nullptr; TickHeader *h_th = nullptr, *d_hth = nullptr;
+    SpecState *h_spec = nullptr, *d_hspec = nullptr;                         // cross-frame speculation (see SpecState)
+    hipError_t carve(uint32_t nslots) {                                     // a fresh, zeroed block with room for nslots group slots
+        hipError_t e = h_block.alloc(HB_RANGES + sizeof(InstanceRange) * (size_t)std::max(nslots, 1u), hipHostMallocMapped | hipHostMallocCoherent);
+        if (e != hipSuccess) return e;
+        h_res = h_block.host<HostResult>(HB_RES); d_hres = h_block.dev<HostResult>(HB_RES); h_spec = h_block.host<SpecState>(HB_SPEC); d_hspec = h_block.dev<SpecState>(HB_SPEC);
+        h_th = h_block.host<TickHeader>(HB_TICK); d_hth = h_block.dev<TickHeader>(HB_TICK); h_ranges = h_block.host<InstanceRange>(HB_RANGES); d_hranges = h_block.dev<InstanceRange>(HB_RANGES);
+        return e;
     }
 };
-struct re_ctx {
-    re_config cfg{};
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[6] = {};
-    std::string err;
-    uint64_t dev_bytes = 0;
-    uint32_t maxlevel = 0;
 
+// LIFETIME RULE.  A member of the context lives in one of two structs, and nothing is released by hand: device and pinned memory is held by DevBuf and
+// Pinned members (re_own.h), which free themselves.
+//   WorldState  what belongs to ONE upload: re_upload_entities starts from `WorldState{}` (free_world), which frees every buffer here and puts every
+//               scalar back to its initialiser.  A new member goes here only if a fresh world must not see its old value.
+//   re_ctx      what lives from re_create to re_destroy and survives uploads: settings, statistics, lazily allocated flows, capacities that are reused.
+struct WorldState : HostBlock {
     // rows.  n = rows in use (every entity ever registered: removed ones keep their row, marked F_DEAD); row_cap = rows the per-entity columns hold
     // (grown by ensure_row_capacity when entities are added after the upload); the ghost instances of the frozen static cache live in rows
     // [ghost_base, ghost_base + ghost_cap) of the id / matrix columns, ghost_base == row_cap.  n_base / ndyn0: rows / dynamic entities of the upload
@@ -113,19 +114,84 @@ struct re_ctx {
     std::unordered_map<uint32_t, uint32_t> id_extra;     // entities added after the upload (and ids reused after a removal): id -> row
     std::unordered_map<uint32_t, uint32_t> dyn_extra;    // rows that got a slot of the dynamic table after the upload: row -> slot
     std::unordered_map<GroupKey, uint32_t, GroupKeyHash> gmap;   // (ModelId, sortable) -> group class
-    uint32_t nslots_cap = 0;                             // InstanceRange capacity of the host result block(s)
     struct AddKeys { uint8_t nk; bool is_static; uint64_t keys[8]; };
     std::unordered_map<uint32_t, AddKeys> add_keys;      // rows an add batch created, with their section decision: consumed by rebucket() (TreeOp kind 4)
-    bool dyn_index(uint32_t r, uint32_t &j) const {      // slot of row r in the dynamic table
-        if (r < ndyn0) { j = r; return true; }
-        auto e = dyn_extra.find(r); if (e == dyn_extra.end()) return false;
-        j = e->second; return true;
-    }
     DevBuf<uint32_t> d_id, d_gclass, d_flags, d_row_cell;
     DevBuf<float> d_mat, d_pos, d_rot, d_scale;
     DevBuf<Aabb> d_aabb, d_orig;
     DevBuf<uint32_t> d_dyn_row, d_dyn_cell; DevBuf<float> d_dyn_vel, d_dyn_acc, d_dyn_rotvel, d_dyn_rotacc;
     DevBuf<uint64_t> d_row_key; DevBuf<uint8_t> d_row_nk; DevBuf<SharedRec> d_shrec; DevBuf<uint32_t> d_counter;
+    // sections
+    uint32_t ncells = 0, nsh = 0;                                           // ncells counts padding slots too
+    DevBuf<uint64_t> d_cell_key; DevBuf<Aabb> d_cell_tight; DevBuf<uint32_t> d_cell_begin, d_cell_nlocal, d_cell_nstatic, d_cell_stamp, d_rows;
+    DevBuf<uint8_t> d_cell_flags;
+    DevBuf<int32_t> d_sh_cells, d_sh_owner; DevBuf<Aabb> d_sh_aabb; DevBuf<uint32_t> d_sh_begin, d_sh_nact, d_sh_nstat; DevBuf<uint8_t> d_sh_cached, d_sh_dirty;
+    DevBuf<uint32_t> d_cell_nghost;                                         // ghost instances per section (see ghost_cap)
+    DevBuf<uint32_t> d_rows_gc;                                             // group class per row-pool entry
+    DevBuf<uint32_t> d_cell_key32, d_chunk_level;                           // compact keys for the stream (worlds of <= 512 sections per axis)
+    // groups
+    DevBuf<uint32_t> d_gc_model, d_gc_rs, d_gc_sort, d_group_count, d_group_begin, d_group_fill;
+    // large visible sets, group tables of <= COUNT_SLOTS_MAX slots: instance counts / running fills per (cursor shard, group slot), two parities alternating by
+    // large-pack frame.  k_pack_large of one frame clears the other parity's arrays for the next; `dirty` tracks arrays that hold something nobody will clear.
+    DevBuf<uint32_t> d_gcount, d_gfill; bool gc_dirty[2] = { false, false };
+    // frame (results land in the lane's HostBlock, written directly by the kernels)
+    bool have_cull = false;
+    DevBuf<FrameParams> d_params;
+    DevBuf<uint32_t> d_item_row, d_item_slot, d_out_ids; DevBuf<float> d_out_mats;
+    DevBuf<FrameHeader> d_hdr; DevBuf<TickHeader> d_th; DevBuf<uint32_t> d_movers, d_oob;
+    DevBuf<SpecState> d_spec;
+    struct PendingCall { uint8_t kind; uint32_t frame; re_camera cam; uint32_t flags; float dt; uint32_t *out_ids; float *out_mats; uint32_t out_cap; uint32_t *out_count; };   // kind 0 = cull_pack, 1 = tick
+    std::vector<PendingCall> pending;                   // calls enqueued since the last resolved synchronisation, in order
+    bool cull_inflight = false, tick_inflight = false;
+    bool deferred_pack = false;                          // RE_CULL_DEFER_PACK: the pack of the last frame, waiting for the next launch
+    bool single_shard = false;                           // see shard_lo
+    // device-side re-bucket bookkeeping (rebucket_on_device): lookup tables, scratch, and the sections whose host mirrors are behind the device
+    DevBuf<uint32_t> d_cell_cap; DevBuf<uint8_t> d_cell_links; std::vector<uint32_t> h_linked_slots;   // (links: shared sections linking each unique section; non-zero keeps a batch on the host)
+    DevBuf<uint64_t> d_base_keys; DevBuf<unsigned long long> d_ovl_keys; DevBuf<uint32_t> d_ovl_slots; uint32_t ovl_cap = 0;
+    bool rb_base_dirty = true, rb_ovl_dirty = true;
+    Pinned chg; DevBuf<WriteOp> d_chg_ops; DevBuf<uint32_t> d_chg_list;   // change batches: mapped staging block of k_apply_small; device scratch of larger batches
+    DevBuf<uint32_t> d_hrb_list; DevBuf<uint8_t> d_hrb_nk; DevBuf<uint64_t> d_hrb_keys;   // scratch of the host-path re-bucket (the movers' new section decisions)
+    // shared world sections on the device path: the table has sh_cap entries with STABLE indices (a retired entry is a hole until a host path rebuilds the
+    // table compactly); ids, row capacities and the id -> index hash are device-only, rebuilt from the host mirrors whenever a host path has touched the table
+    uint32_t sh_cap = 0; bool rb_sh_dirty = true;
+    DevBuf<uint64_t> d_sh_keys; DevBuf<uint8_t> d_sh_nk, d_cell_inact; DevBuf<uint32_t> d_sh_rowcap, d_sh_hidx; DevBuf<unsigned long long> d_sh_hkeys;
+    std::vector<uint32_t> sh_free, stale_shared;        // holes of the table (indices a new shared section may take); entries the device changed since the host mirrors were brought up to date
+    struct Rb2Scratch {
+        uint32_t cap = 0;                                 // movers the buffers are sized for
+        DevBuf<uint64_t> key, key2, ord, ord_s, kgath, ksorted1, ksorted2, mk, pair_key, pair_key_s; DevBuf<uint32_t> row, idx, perm_a, perm1, perm2, host_list, refold, tmp_u, tmp_s, free_u, free_off, free_s, pair_seg, pair_seg_s;
+        DevBuf<uint8_t> mnk, tmp; DevBuf<Rb2Seg> segs_u; DevBuf<Rb2ShSeg> segs_s; DevBuf<Rb2Status> status;
+        // pinned host staging of everything that travels between the host and the device inside one batch (status blocks, free slots, the segments' outcome): copies from / to
+        // pageable memory cost 15-20 us each, and a batch made eight of them -- most of a small batch's time
+        Pinned pin;
+        bool status_clean = false; uint32_t status_pool = 0;                  // the device status block was reset by the last batch's final read-back and holds this pool fill
+        Rb2Status *h_status = nullptr, *d_h_status = nullptr; uint32_t *h_seq = nullptr, *d_h_seq = nullptr, seq = 0;      // (d_h_*: the device's view of the mapped block)
+        uint32_t *h_free_off = nullptr, *h_free_u = nullptr, *h_free_s = nullptr, *h_keep = nullptr; Rb2Seg *h_segs_u = nullptr; Rb2ShSeg *h_segs_s = nullptr;
+    } rb2;
+    std::vector<uint32_t> stale_slots;                   // sections patched on the device since the host mirrors (h_cell_*, h_rows, h_row_*, extra_slots) were last brought up to date
+    DevBuf<uint32_t> d_light_rows, d_light_out; bool light_rows_dirty = true;   // rows that carry a FindLightType (members of their section's light set); ascending EntityId on the device
+    // LightInformation (re_set_light_information) by row: the host copy is the truth (nothing on the device writes it); the device column d_li follows the light list
+    std::unordered_map<uint32_t, re_light_information> h_li; std::vector<re_light_information> h_li_col; DevBuf<re_light_information> d_li; bool li_dirty = true;
+    // entity logic (re_logic_list).  Entity types by row: the host copy is the truth (nothing on the device writes them).  On the device: the rows whose type is in
+    // the table, ascending, and next to each its word (table index | which << 16); rebuilt only when a setter or an upload has marked them dirty -- moves,
+    // make-static, wake-up and deletes need no rebuild (the kernel reads the live flags, row_cell and stamps).
+    std::vector<uint64_t> h_type; std::vector<uint8_t> h_typed;                // [row]; rows beyond the vectors carry no type
+    DevBuf<uint32_t> d_logic_rows, d_logic_words; DevBuf<unsigned long long> d_logic_out; uint32_t logic_n = 0; bool logic_dirty = true;
+};
+struct DeviceBytes { uint64_t dev_bytes = 0; };      // the counter accounted buffers book into: a base in front of WorldState, so that it outlives every buffer of the context
+struct re_ctx : DeviceBytes, WorldState {
+    re_config cfg{};
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[6] = {};
+    std::string err;
+    uint32_t maxlevel = 0;
+
+    uint32_t nslots_cap = 0;                             // InstanceRange capacity of the host result block(s)
+    bool dyn_index(uint32_t r, uint32_t &j) const {      // slot of row r in the dynamic table
+        if (r < ndyn0) { j = r; return true; }
+        auto e = dyn_extra.find(r); if (e == dyn_extra.end()) return false;
+        j = e->second; return true;
+    }
     std::vector<uint32_t> h_id, h_flags, h_dyn_row;      // host mirrors of the immutable id column / upload flags / dynamic-row list
     uint32_t n_rebuilds = 0;
     bool has_rotvel = false; uint32_t n_dead = 0;         // n_dead: rows removed by out-of-bounds ticks (upper bound on uncounted reservations)
@@ -140,11 +206,8 @@ struct re_ctx {
         if (p == id_rows.end() || p->first != id) return false;
         *row = p->second; return true;
     }
-    // sections
-    uint32_t ncells = 0, nsh = 0, nrows_csr = 0, n_real_sections = 0;   // ncells counts padding slots too
-    DevBuf<uint64_t> d_cell_key; DevBuf<Aabb> d_cell_tight; DevBuf<uint32_t> d_cell_begin, d_cell_nlocal, d_cell_nstatic, d_cell_stamp, d_rows;
-    DevBuf<uint8_t> d_cell_flags;
-    DevBuf<int32_t> d_sh_cells, d_sh_owner; DevBuf<Aabb> d_sh_aabb; DevBuf<uint32_t> d_sh_begin, d_sh_nact, d_sh_nstat; DevBuf<uint8_t> d_sh_cached, d_sh_dirty;
+    // sections (host side)
+    uint32_t nrows_csr = 0, n_real_sections = 0;
     std::vector<uint64_t> h_cell_key;
     // host copies the incremental re-bucket needs: per-row section decision, and the shared-section ids in device order
     std::vector<uint64_t> h_row_key; std::vector<uint8_t> h_row_nk; std::vector<uint32_t> h_row_cell, h_gclass;
@@ -167,69 +230,56 @@ struct re_ctx {
     uint32_t pool_used = 0, pool_cap = 0, n_patches = 0;
     // ghost instances (snapshot copies of the frozen static render cache): rows n .. n + n_ghost of the id / matrix columns
     uint32_t ghost_cap = 0, n_ghost = 0; std::vector<uint32_t> h_ghost_gc; std::map<uint64_t, std::vector<uint32_t>> ghost_map;   // per section key: its ghost rows
-    DevBuf<uint32_t> d_cell_nghost; std::vector<uint32_t> h_cell_ng;
+    std::vector<uint32_t> h_cell_ng;
     // collision broad phase (re_collide): lists allocated at the first call
-    uint32_t user_row = ROW_CELL_NONE; DevBuf<ColHeader> d_col_hdr; DevBuf<ColRegion> d_col_region; DevBuf<uint32_t> d_col_high; DevBuf<ColShared> d_col_shared; DevBuf<ColMoved> d_col_moved; DevBuf<ColNear> d_col_near; ColHeader *h_col = nullptr, *d_hcol = nullptr; uint32_t col_calls = 0;
+    uint32_t user_row = ROW_CELL_NONE; DevBuf<ColHeader> d_col_hdr; DevBuf<ColRegion> d_col_region; DevBuf<uint32_t> d_col_high; DevBuf<ColShared> d_col_shared; DevBuf<ColMoved> d_col_moved; DevBuf<ColNear> d_col_near; Pinned col_pub; ColHeader *h_col = nullptr, *d_hcol = nullptr; uint32_t col_calls = 0;   // (h_col, d_hcol: the mapped block col_pub)
     DevBuf<uint8_t> d_row_moved; DevBuf<unsigned long long> d_col_tab; DevBuf<uint2> d_col_pairs; uint32_t col_moved_cap = 0, col_tab_size = 0, col_pair_cap = 0, col_rows = 0;
     DevBuf<HashEntry> d_htab; uint32_t htab_mask = 0, htab_keys = 0; uint32_t probe_frames = 0;   // RE_CFG_PROBE: key -> slot table of the probe path (k_probe_cull)
     std::set<uint64_t> dormant_cached;                  // sections with ghosts that were cached when they were emptied: the reference's cache entry outlives the section and shows again when the section is re-created
     std::set<uint32_t> h_uncached;                       // rows made static after the static render cache froze: in the tree's static sets, not drawn
     // groups
     uint32_t ngclass = 0, nslots = 0;
-    DevBuf<uint32_t> d_gc_model, d_gc_rs, d_gc_sort, d_group_count, d_group_begin, d_group_fill;
-    // large visible sets, group tables of <= COUNT_SLOTS_MAX slots: instance counts / running fills per (cursor shard, group slot), two parities alternating by
-    // large-pack frame.  k_pack_large of one frame clears the other parity's arrays for the next; `dirty` tracks arrays that hold something nobody will clear.
-    DevBuf<uint32_t> d_gcount, d_gfill; bool gc_dirty[2] = { false, false }; uint32_t large_seq = 0;
+    uint32_t large_seq = 0;                              // large-pack frames so far (the parity of d_gcount / d_gfill)
     // per-model level-of-view bands (level_views.custom): kept across uploads, like a model registration; device tables rebuilt when they or the group classes change
     struct CustomLod { uint32_t model, rs, n; float lmin[8], lmax[8]; };
     std::vector<CustomLod> custom_lod; std::vector<GroupKey> h_gkeys;
     DevBuf<uint32_t> d_gc_lodtab, d_lod_n; DevBuf<float> d_lod_min, d_lod_max; bool lod_tables_on = false;
     // frame
-    uint32_t frame = 0; bool have_cull = false;
-    DevBuf<uint32_t> d_rows_gc; std::vector<uint32_t> h_sh_begin;   // group class per row-pool entry; pool offsets of the shared sections' members
-    DevBuf<uint32_t> d_cell_key32, d_chunk_level; bool key32 = false; PBox32Table PB32{};   // compact keys for the stream (worlds of <= 512 sections per axis)
-    FrameParams P{}; PBoxTable PB{}; DevBuf<FrameParams> d_params;
+    uint32_t frame = 0;
+    std::vector<uint32_t> h_sh_begin;                    // pool offsets of the shared sections' members
+    bool key32 = false; PBox32Table PB32{};              // compact keys for the stream (worlds of <= 512 sections per axis)
+    FrameParams P{}; PBoxTable PB{};
 #ifdef RE_EXP_STAMPS
     DevBuf<unsigned long long> d_timeline;
 #endif
     uint32_t nlists = 0, pred_candidates = 0;             // nlists: 512-key chunks == waves of k_scan_cull
     uint32_t item_cap = 0, out_cap = 0, list_cap = 0;
-    DevBuf<uint32_t> d_item_row, d_item_slot, d_out_ids; DevBuf<float> d_out_mats;
     uint32_t *ext_out_ids = nullptr; float *ext_out_mats = nullptr; uint32_t ext_out_cap = 0; uint32_t *ext_out_count = nullptr;
-    DevBuf<FrameHeader> d_hdr; DevBuf<TickHeader> d_th; DevBuf<uint32_t> d_movers, d_oob;
-    // results land in mapped pinned host memory, written directly by the kernels (d_* = device view)
-    SpecState *h_spec = nullptr, *d_hspec = nullptr; DevBuf<SpecState> d_spec;     // cross-frame speculation (see SpecState)
-    struct PendingCall { uint8_t kind; uint32_t frame; re_camera cam; uint32_t flags; float dt; uint32_t *out_ids; float *out_mats; uint32_t out_cap; uint32_t *out_count; };   // kind 0 = cull_pack, 1 = tick
     std::vector<uint32_t> h_oob_ids;                    // entities removed because they left the world, since the last re_get_out_of_bounds
-    std::vector<PendingCall> pending;                   // calls enqueued since the last resolved synchronisation, in order
-    HostResult *h_res = nullptr, *d_hres = nullptr; InstanceRange *h_ranges = nullptr, *d_hranges = nullptr; TickHeader *h_th = nullptr, *d_hth = nullptr;
-    void *h_block = nullptr;                           // the one mapped, coherent host block those four live in (alloc_host_block)
     uint32_t n_seal_waits = 0, n_sync_fallbacks = 0;  // a polled block whose seal did not agree at first sight / that needed a stream synchronise: both stay 0 when the publication protocol holds
     bool th_clean = true; uint32_t pred_total = 0;
     std::vector<re_instance_range> groups_out;
-    bool cull_inflight = false, tick_inflight = false;
     bool tick_published = false;                      // the tick in flight publishes its counters itself (synchronous ticks; asynchronous ones are settled by resolve())
     uint32_t tick_frame = 0xFFFFFFFFu;                // frame of the last tick issued
     uint32_t tick_seq = 0;                            // synchronous ticks issued with a kernel: the last wave of k_tick writes the number into h_th->ticket (tick_sign_off)
     bool timings_on = false;                          // re_get_timings was asked for: synchronous frames record their kernel events (5 event records cost ~12 us per frame)
-    bool deferred_pack = false; FusedPack deferred{}; uint32_t deferred_grid = 0, n_fused_frames = 0;
+    FusedPack deferred{}; uint32_t deferred_grid = 0, n_fused_frames = 0;   // the deferred pack (WorldState::deferred_pack)
     // RE_CULL_TWO_LANES: a second set of per-frame resources ("lane": stream, frame headers, instance lists, section stamps, frame
     // parameters, packed output, result block, deferred pack).  The members above/below always are those of the CURRENT lane; the other
     // lane's are parked here and swapped in by switch_lane().  Frames of a static fly-through alternate lanes, so the launches of
     // consecutive frames sit on different streams and overlap; everything else first drains the other lane (drain_other_lane).
-    struct LanePark {
+    struct LanePark : HostBlock {
         hipStream_t stream = nullptr; DevBuf<FrameHeader> d_hdr; DevBuf<uint32_t> d_item_row, d_item_slot, d_out_ids, d_cell_stamp; DevBuf<float> d_out_mats; DevBuf<FrameParams> d_params;
-        HostResult *h_res = nullptr, *d_hres = nullptr; InstanceRange *h_ranges = nullptr, *d_hranges = nullptr; void *h_block = nullptr;
         bool deferred_pack = false; FusedPack deferred{}; uint32_t deferred_grid = 0, lane_seq = 0; bool busy = false;
     } park;
-    bool park_ready = false, lane_busy = false; uint32_t lane_seq = 0, lane_id = 0, n_lane_switches = 0;   // RE_CULL_DEFER_PACK: the pack of the last frame, waiting for the next launch
+    bool park_ready = false, lane_busy = false; uint32_t lane_seq = 0, lane_id = 0, n_lane_switches = 0;
     re_tick_result last_tick{};
     // The instance list is CURSOR_SHARDS segments with one cursor each, and a wave reserves in segment (wave index mod 8): sections that sit in few
     // waves (one crowded section, a cluster) can fill one segment while the list as a whole has room.  The pack kernels report that
     // (RESULT_SEGMENT_OVERFLOW); finish_cull then redoes the frame with the list as ONE segment -- which holds every instance of the world twice
     // (duplicates mode) by construction -- and the context stays in that mode until the next upload.
     uint64_t shard_lo = 0, shard_hi = 0; std::vector<uint32_t> moved_rows;   // re_set_shard_range: the keys this context owns; rows re-bucketed since the last re_list_migrants
-    bool single_shard = false; uint32_t n_segment_redos = 0; re_camera last_cam{}; uint32_t last_cull_flags = 0;
+    uint32_t n_segment_redos = 0; re_camera last_cam{}; uint32_t last_cull_flags = 0;
     // what the last frame's pack was launched with, so that it can be run again into other output buffers (the second, variable-length round of the
     // multi-GPU exchange when a rank's visible set outgrew its slab)
     struct LastPack { int kind = 0; FrameHeader *hdr = nullptr, *hdr_next = nullptr; PackArgs A{}; ItemSink K{}; uint32_t grid = 0, nrows = 0, par = 0; PackLargeArgs L{}; } last_pack;   // kind: 1 k_pack_small, 2 k_pack_large, 3 count / scan / scatter
@@ -239,36 +289,12 @@ struct re_ctx {
         void *comm = nullptr; bool owned = false; int rank = 0, n = 1; uint32_t cap = 0, words = 0, seq = 0; int last = -1, pending = -1;
         DevBuf<uint32_t> slab[2], recv[2], big_ids; DevBuf<float> big_mats; uint32_t big_cap = 0;
         std::vector<uint32_t> counts; uint32_t n_second_rounds = 0, n_regathers = 0;
-        uint32_t *h_hdr = nullptr, *d_hhdr = nullptr, hdr_seq = 0;          // the gathered slab headers in mapped host memory ([n ranks][4 words], then the sequence word k_gather_headers publishes)
+        Pinned hdr_pub; uint32_t *h_hdr = nullptr, *d_hhdr = nullptr, hdr_seq = 0;          // (h_hdr, d_hhdr: the mapped block hdr_pub) the gathered slab headers in mapped host memory ([n ranks][4 words], then the sequence word k_gather_headers publishes)
     } comm;
     float t_cull = 0, t_pack = 0, t_tick = 0; bool timed_frame = false, timed_tick = false;
-    // device-side re-bucket bookkeeping (rebucket_on_device): lookup tables, scratch, and the sections whose host mirrors are behind the device
-    DevBuf<uint32_t> d_cell_cap; DevBuf<uint8_t> d_cell_links; std::vector<uint32_t> h_linked_slots;   // (links: shared sections linking each unique section; non-zero keeps a batch on the host)
-    DevBuf<uint64_t> d_base_keys; DevBuf<unsigned long long> d_ovl_keys; DevBuf<uint32_t> d_ovl_slots; uint32_t ovl_cap = 0, ovl_count = 0;
-    bool rb_base_dirty = true, rb_ovl_dirty = true;
-    uint8_t *h_chg = nullptr, *d_chg = nullptr; DevBuf<WriteOp> d_chg_ops; DevBuf<uint32_t> d_chg_list;   // change batches: mapped staging block of k_apply_small; device scratch of larger batches
-    DevBuf<uint32_t> d_hrb_list; DevBuf<uint8_t> d_hrb_nk; DevBuf<uint64_t> d_hrb_keys;   // scratch of the host-path re-bucket (the movers' new section decisions)
-    // shared world sections on the device path: the table has sh_cap entries with STABLE indices (a retired entry is a hole until a host path rebuilds the
-    // table compactly); ids, row capacities and the id -> index hash are device-only, rebuilt from the host mirrors whenever a host path has touched the table
-    uint32_t sh_cap = 0, sh_hmask = 0, sh_hash_used = 0; bool rb_sh_dirty = true;   // (sh_hash_used: entries of the id -> index hash, retired ones included)
-    DevBuf<uint64_t> d_sh_keys; DevBuf<uint8_t> d_sh_nk, d_cell_inact; DevBuf<uint32_t> d_sh_rowcap, d_sh_hidx; DevBuf<unsigned long long> d_sh_hkeys;
-    std::vector<uint32_t> sh_free, stale_shared;        // holes of the table (indices a new shared section may take); entries the device changed since the host mirrors were brought up to date
-    struct Rb2Scratch {
-        uint32_t cap = 0;                                 // movers the buffers are sized for
-        DevBuf<uint64_t> key, key2, ord, ord_s, kgath, ksorted1, ksorted2, mk, pair_key, pair_key_s; DevBuf<uint32_t> row, idx, perm_a, perm1, perm2, host_list, refold, tmp_u, tmp_s, free_u, free_off, free_s, pair_seg, pair_seg_s;
-        DevBuf<uint8_t> mnk, tmp; DevBuf<Rb2Seg> segs_u; DevBuf<Rb2ShSeg> segs_s; DevBuf<Rb2Status> status;
-        // pinned host staging of everything that travels between the host and the device inside one batch (status blocks, free slots, the segments' outcome): copies from / to
-        // pageable memory cost 15-20 us each, and a batch made eight of them -- most of a small batch's time
-        uint8_t *pin = nullptr, *d_pin = nullptr; size_t pin_bytes = 0;     // (d_pin: the device's address of the mapped block)
-        bool status_clean = false; uint32_t status_pool = 0;                  // the device status block was reset by the last batch's final read-back and holds this pool fill
-        Rb2Status *h_status = nullptr, *d_h_status = nullptr; uint32_t *h_seq = nullptr, *d_h_seq = nullptr, seq = 0;      // (d_h_*: the device's view of the mapped block)
-        uint32_t *h_free_off = nullptr, *h_free_u = nullptr, *h_free_s = nullptr, *h_keep = nullptr; Rb2Seg *h_segs_u = nullptr; Rb2ShSeg *h_segs_s = nullptr;
-    } rb2;
-    std::vector<uint32_t> stale_slots;                   // sections patched on the device since the host mirrors (h_cell_*, h_rows, h_row_*, extra_slots) were last brought up to date
+    uint32_t ovl_count = 0, sh_hmask = 0, sh_hash_used = 0;   // entries of the overlay; mask of the shared id -> index hash and its entries, retired ones included
     uint32_t n_device_rebuckets = 0, n_host_rebuckets = 0, n_phantom = 0, last_added_rejected = 0, slack_boost = 1;
-    std::vector<uint32_t> h_light_rows; DevBuf<uint32_t> d_light_rows, d_light_out; bool light_rows_dirty = true;   // rows that carry a FindLightType (members of their section's light set); ascending EntityId on the device
-    // LightInformation (re_set_light_information) by row: the host copy is the truth (nothing on the device writes it); the device column d_li follows the light list
-    std::unordered_map<uint32_t, re_light_information> h_li; std::vector<re_light_information> h_li_col; DevBuf<re_light_information> d_li; bool li_dirty = true; bool li_complete[3] = {};
+    std::vector<uint32_t> h_light_rows; bool li_complete[3] = {};   // rows that carry a FindLightType, host copy (see d_light_rows)
     uint64_t li_epoch = 0, rows_epoch = 0;             // bumped when the LightInformation column is rebuilt / when rows may have been added, removed or regrouped (shadow flow caches)
     std::vector<hipEvent_t> k1_events; uint32_t k1_used = 0, k1_every = 1, k1_seen = 0, k1_kind = 0; bool k1_timing = false;   // per-launch timing of one kernel (re_timing_begin): k_scan_cull, k_tick or k_pack_large
 
@@ -276,12 +302,9 @@ struct re_ctx {
         char buf[512]; va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
         err = buf; return code;
     }
-    // entity logic (re_logic_list).  Entity types by row: the host copy is the truth (nothing on the device writes them).  The logic table belongs to the flow and
-    // survives uploads.  On the device: the rows whose type is in the table, ascending, and next to each its word (table index | which << 16); rebuilt only when a
-    // setter or an upload has marked them dirty -- moves, make-static, wake-up and deletes need no rebuild (the kernel reads the live flags, row_cell and stamps).
-    std::vector<uint64_t> h_type; std::vector<uint8_t> h_typed;                // [row]; rows beyond the vectors carry no type
+    // entity logic (re_logic_list): the logic table and the channel belong to the flow and survive uploads (the row lists are the world's: WorldState)
     std::vector<re_entity_logic> logic_table; std::unordered_map<uint64_t, uint32_t> logic_index;   // TypeIdentifier -> table index
-    DevBuf<uint32_t> d_logic_rows, d_logic_words; DevBuf<unsigned long long> d_logic_out; ListChannel logic; uint32_t logic_n = 0; bool logic_dirty = true;
+    ListChannel logic;
     QueryFlow<BoxQuery> boxq; QueryFlow<SegQuery> segq;                        // tree queries (re_query_boxes, re_query_segments)
 };
 
@@ -313,8 +336,7 @@ struct StreamSync { re_ctx *c; hipStream_t st; int operator()() const { HIPCHK(c
 int ListChannel::open(re_ctx *c) {
     if (hdr.p) return RE_OK;
     HIPCHK(c, hdr.alloc(1, nullptr)); HIPCHK(c, hipMemsetAsync(hdr.p, 0, sizeof(LogicHeader), c->stream));      // cleared once; every call leaves it clean again
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&h_pub), sizeof(LogicPublished), hipHostMallocMapped | hipHostMallocCoherent)); memset(h_pub, 0, sizeof(LogicPublished));
-    HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&d_pub), h_pub, 0));
+    HIPCHK(c, pub.alloc(sizeof(LogicPublished), hipHostMallocMapped | hipHostMallocCoherent)); h_pub = pub.host<LogicPublished>(); d_pub = pub.dev<LogicPublished>();
     return RE_OK;
 }
 int ListChannel::wait(re_ctx *c, uint32_t seq, uint32_t *n) {
@@ -338,21 +360,6 @@ IssueClock g_issue_clock;
 static const bool g_time_rebucket = getenv("RE_EXP_TIME_REBUCKET") != nullptr;   // RE_EXP_TIME_REBUCKET=1: the phases of every re-bucket and section patch, on stderr
 static void report_issue_clock() { g_issue_clock.report(); g_issue_clock.n = 0; g_issue_clock.params = g_issue_clock.spans = g_issue_clock.scan = g_issue_clock.pack = g_issue_clock.wait = g_issue_clock.finish = 0; }
 
-// Everything the kernels publish to the polling host thread lives in ONE block of mapped, coherent pinned host memory per frame lane
-// (hipHostMallocMapped | hipHostMallocCoherent): the frame result at 0, the speculation word at 128, the tick counters at 256, the
-// InstanceRange table from 8192 on.  (Round 1 used four separate hipHostMalloc(Mapped) blocks; what made its group table arrive after
-// the "frame done" word was not the number of blocks but the plain store of that word -- see publish_to_host in re_kernels.h.)
-constexpr size_t HB_RES = 0, HB_SPEC = 128, HB_TICK = 256, HB_RANGES = 8192;
-static_assert(sizeof(HostResult) <= HB_SPEC && sizeof(SpecState) <= HB_TICK - HB_SPEC && HB_TICK + sizeof(TickHeader) <= HB_RANGES, "host block layout");
-static hipError_t alloc_host_block(uint32_t nslots, void **host, void **dev) {
-    const size_t bytes = HB_RANGES + sizeof(InstanceRange) * (size_t)std::max(nslots, 1u);
-    hipError_t e = hipHostMalloc(host, bytes, hipHostMallocMapped | hipHostMallocCoherent);
-    if (e != hipSuccess) return e;
-    memset(*host, 0, bytes);
-    return hipHostGetDevicePointer(dev, *host, 0);
-}
-template <typename T> static inline T *hb_at(void *base, size_t off) { return reinterpret_cast<T *>(static_cast<char *>(base) + off); }
-
 extern "C" const char *re_last_error(const re_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
 extern "C" int re_create(const re_config *cfg, re_ctx **out) try {
@@ -374,47 +381,11 @@ extern "C" int re_create(const re_config *cfg, re_ctx **out) try {
     return RE_OK;
 } RE_ABI_GUARD_NOCTX(g_create_error, "re_create")
 
-static void release_rb2(re_ctx *c) {
-    re_ctx::Rb2Scratch &B = c->rb2;
-    for (DevBuf<uint64_t> *b : { &B.key, &B.key2, &B.ord, &B.ord_s, &B.kgath, &B.ksorted1, &B.ksorted2, &B.mk, &B.pair_key, &B.pair_key_s }) b->release(nullptr);
-    for (DevBuf<uint32_t> *b : { &B.row, &B.idx, &B.perm_a, &B.perm1, &B.perm2, &B.host_list, &B.refold, &B.tmp_u, &B.tmp_s, &B.free_u, &B.free_off, &B.free_s, &B.pair_seg, &B.pair_seg_s }) b->release(nullptr);
-    B.mnk.release(nullptr); B.tmp.release(nullptr); B.segs_u.release(nullptr); B.segs_s.release(nullptr); B.status.release(nullptr); B.cap = 0;
-    if (B.pin) { (void)hipHostFree(B.pin); B.pin = nullptr; B.pin_bytes = 0; }
-}
-static void drop_collision_scratch(re_ctx *c) { c->d_row_moved.release(nullptr); c->d_col_moved.release(nullptr); c->d_col_tab.release(nullptr); c->col_moved_cap = 0; }   // sized by the row and dynamic-slot capacities: dropped where those change, sized again at the next re_collide
-// What re_collide, re_logic_list and re_query_boxes allocate lazily and keep across uploads (the logic flow's row lists and record buffer belong to the world: free_world).
-static void release_flows(re_ctx *c) {
-    c->d_col_hdr.release(nullptr); c->d_col_region.release(nullptr); c->d_col_high.release(nullptr); c->d_col_shared.release(nullptr); c->d_col_near.release(nullptr); c->d_col_pairs.release(nullptr); c->col_pair_cap = 0; drop_collision_scratch(c);
-    if (c->h_col) { (void)hipHostFree(c->h_col); c->h_col = c->d_hcol = nullptr; }
-    c->logic.close(); c->boxq.release(); c->segq.release();
-}
-static void free_world(re_ctx *c) {
-    uint64_t *a = &c->dev_bytes;
-    c->d_light_rows.release(nullptr); c->d_light_out.release(nullptr); c->light_rows_dirty = true;
-    c->h_li.clear(); c->h_li_col.clear(); c->d_li.release(nullptr); c->li_dirty = true;
-    c->h_type.clear(); c->h_typed.clear(); c->d_logic_rows.release(nullptr); c->d_logic_words.release(nullptr); c->d_logic_out.release(nullptr); c->logic_n = 0; c->logic_dirty = true;   // (the logic table stays)
-    c->d_cell_cap.release(a); c->d_cell_links.release(a); c->h_linked_slots.clear(); c->d_base_keys.release(a); c->d_ovl_keys.release(nullptr); c->d_ovl_slots.release(nullptr); c->ovl_cap = 0; c->rb_base_dirty = c->rb_ovl_dirty = true; c->stale_slots.clear();
-    c->d_hrb_list.release(nullptr); c->d_hrb_nk.release(nullptr); c->d_hrb_keys.release(nullptr); c->d_chg_ops.release(nullptr); c->d_chg_list.release(nullptr);
-    if (c->h_chg) { (void)hipHostFree(c->h_chg); c->h_chg = nullptr; c->d_chg = nullptr; }
-    c->d_sh_keys.release(nullptr); c->d_sh_nk.release(nullptr); c->d_cell_inact.release(nullptr); c->d_sh_rowcap.release(nullptr); c->d_sh_hidx.release(nullptr); c->d_sh_hkeys.release(nullptr);
-    c->sh_cap = 0; c->rb_sh_dirty = true; c->sh_free.clear(); c->stale_shared.clear(); release_rb2(c);
-    c->d_id.release(a); c->d_gclass.release(a); c->d_flags.release(a); c->d_row_cell.release(a); c->d_mat.release(a); c->d_pos.release(a); c->d_rot.release(a);
-    c->d_scale.release(a); c->d_aabb.release(a); c->d_orig.release(a); c->d_dyn_row.release(a); c->d_dyn_cell.release(a); c->d_dyn_vel.release(a); c->d_dyn_acc.release(a);
-    c->d_dyn_rotvel.release(a); c->d_dyn_rotacc.release(a); c->d_row_key.release(a); c->d_row_nk.release(a); c->d_shrec.release(a); c->d_counter.release(a);
-    c->d_cell_key.release(a); c->d_cell_tight.release(a); c->d_cell_begin.release(a); c->d_cell_nlocal.release(a); c->d_cell_nstatic.release(a);
-    c->d_cell_stamp.release(a); c->d_rows.release(a); c->d_cell_flags.release(a); c->d_sh_cells.release(a); c->d_sh_owner.release(a); c->d_sh_aabb.release(a);
-    c->d_sh_begin.release(a); c->d_sh_nact.release(a); c->d_sh_nstat.release(a); c->d_sh_cached.release(a); c->d_sh_dirty.release(a);
-    c->d_gc_model.release(a); c->d_gc_rs.release(a); c->d_gc_sort.release(a); c->d_group_count.release(a); c->d_group_begin.release(a); c->d_group_fill.release(a);
-    c->d_gcount.release(a); c->d_gfill.release(a); c->gc_dirty[0] = c->gc_dirty[1] = false;
-    c->d_item_row.release(a); c->d_item_slot.release(a); c->d_out_ids.release(a); c->d_out_mats.release(a);
-    c->d_hdr.release(a); c->d_th.release(a); c->d_params.release(a); c->d_movers.release(a); c->d_oob.release(a);
-    if (c->h_block) { (void)hipHostFree(c->h_block); c->h_block = nullptr; }      // one block: frame result, speculation word, tick counters, group table
-    c->h_res = nullptr; c->h_ranges = nullptr; c->h_th = nullptr; c->h_spec = nullptr;
-    c->d_spec.release(nullptr); c->pending.clear();
-    c->single_shard = false; c->id_extra.clear(); c->dyn_extra.clear(); c->gmap.clear(); c->add_keys.clear();
-    c->row_cap = c->ghost_base = c->n_base = c->ndyn0 = c->dyn_cap = 0;
-    c->n = c->ndyn = c->ncells = c->nsh = 0; c->have_cull = false; c->cull_inflight = c->tick_inflight = false; c->deferred_pack = false;
-}
+static void drop_collision_scratch(re_ctx *c) { c->col_moved_cap = 0; }   // the moved-row scratch is sized by the row and dynamic-slot capacities: sized (and cleared) again at the next re_collide where those change
+// A fresh world: every buffer of the last upload is freed, every member of WorldState is back at its initialiser.
+static void free_world(re_ctx *c) { static_cast<WorldState &>(*c) = WorldState{}; }
+
+extern "C" uint64_t re_debug_live_allocations(void) { return live_allocations(); }
 
 extern "C" void re_destroy(re_ctx *c) try {
     if (!c) return;
@@ -423,12 +394,10 @@ extern "C" void re_destroy(re_ctx *c) try {
     if (c->park_ready) { (void)drain_other_lane(c); free_second_lane(c); }
     if (c->stream) (void)sync_stream(c->stream);
     if (c->comm.comm) comm_release(c);
-    free_world(c);
-    release_flows(c);
     for (auto &ev : c->ev) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->k1_events) (void)hipEventDestroy(ev);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                                               // (every buffer frees itself, after the synchronise above)
 } catch (...) {}
 
 static RowArrays row_arrays(re_ctx *c) {
@@ -452,10 +421,10 @@ static void collect_row_gc(const re_ctx *c, uint32_t r, std::vector<Pair32> &out
 }
 static int upload_row_gc(re_ctx *c, const std::vector<Pair32> &pairs) {
     if (pairs.empty()) return RE_OK;
-    Pair32 *d = nullptr; HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&d), pairs.size() * sizeof(Pair32)));
-    HIPCHK(c, hipMemcpyAsync(d, pairs.data(), pairs.size() * sizeof(Pair32), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_scatter32, dim3(((uint32_t)pairs.size() + 255) / 256), dim3(256), 0, c->stream, (uint32_t)pairs.size(), d, c->d_rows_gc.p);
-    HIPCHK(c, sync_stream(c->stream)); (void)hipFree(d);
+    DevBuf<Pair32> d; HIPCHK(c, d.alloc(pairs.size(), nullptr));
+    HIPCHK(c, hipMemcpyAsync(d.p, pairs.data(), pairs.size() * sizeof(Pair32), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_scatter32, dim3(((uint32_t)pairs.size() + 255) / 256), dim3(256), 0, c->stream, (uint32_t)pairs.size(), d.p, c->d_rows_gc.p);
+    HIPCHK(c, sync_stream(c->stream));
     return RE_OK;
 }
 
@@ -728,10 +697,9 @@ static int build_sections(re_ctx *c, const std::vector<uint64_t> &row_key, const
     HIPCHK(c, sync_stream(st));
     c->nlists = std::max(1u, (uint32_t)((ncells + wave_keys - 1) / wave_keys));       // waves of k_scan_cull
     HIPCHK(c, sync_stream(st));
-    d_refold.release(nullptr); d_carried.release(nullptr);
-    if (c->cfg.flags & RE_CFG_PROBE) {                                      // key -> slot table at load <= 0.5 (tombstones of later patches included until the next full build)
+    if (c->cfg.flags & RE_CFG_PROBE) {                                     // key -> slot table at load <= 0.5 (tombstones of later patches included until the next full build)
         uint32_t sz = 1024; while (sz < 2u * (uint32_t)std::min<size_t>(ncells + 1u, 1u << 30)) sz <<= 1;
-        if (c->htab_mask + 1u != sz) { c->d_htab.release(acct); HIPCHK(c, c->d_htab.alloc(sz, acct)); c->htab_mask = sz - 1u; }
+        if (c->htab_mask + 1u != sz) { HIPCHK(c, c->d_htab.alloc(sz, acct)); c->htab_mask = sz - 1u; }
         HIPCHK(c, hipMemsetAsync(c->d_htab.p, 0xFF, (size_t)sz * sizeof(HashEntry), st));
         if (ncells) hipLaunchKernelGGL(k_hash_build, dim3((ncells + 255) / 256), dim3(256), 0, st, ncells, c->d_cell_key.p, c->d_htab.p, c->htab_mask);
         HIPCHK(c, hipGetLastError()); HIPCHK(c, sync_stream(st));
@@ -912,7 +880,7 @@ extern "C" int re_upload_entities(re_ctx *c, const re_entities *E, uint32_t *n_r
     uint32_t rejected = 0;
     for (uint32_t r = 0; r < n; r++) if (row_nk[r] == 0) rejected++;
     if (n_rejected) *n_rejected = rejected;
-    c->d_shrec.release(acct);
+    c->d_shrec.release();                                                       // (only the upload's kernel writes it: the memory is back before the section build)
     c->h_row_key = row_key; c->h_row_nk = row_nk; c->h_gclass = gclass; c->h_row_shared_keys.clear(); c->h_uncached.clear(); c->h_oob_ids.clear(); c->pending.clear();
     for (const SharedRec &sr : shrec) { std::array<uint64_t, 8> a; memcpy(a.data(), sr.keys, sizeof sr.keys); c->h_row_shared_keys[sr.row] = a; }
     int rc = build_sections(c, row_key, row_nk, shrec, flags);
@@ -923,16 +891,8 @@ extern "C" int re_upload_entities(re_ctx *c, const re_entities *E, uint32_t *n_r
     c->item_cap = c->out_cap = c->list_cap = 0;
     { int rc2 = size_frame_buffers(c); if (rc2 != RE_OK) return rc2; }
     HIPCHK(c, c->d_hdr.alloc(NUM_FRAME_HEADERS, acct)); HIPCHK(c, c->d_th.alloc(1, acct)); HIPCHK(c, c->d_params.alloc(1, acct));
-    {
-        void *hb = nullptr, *db = nullptr;
-        c->nslots_cap = std::max(2u * c->nslots, 1024u);                           // head-room: entities added later may bring new (ModelId, sortable) groups
-        HIPCHK(c, alloc_host_block(c->nslots_cap, &hb, &db));
-        c->h_block = hb;
-        c->h_res = hb_at<HostResult>(hb, HB_RES); c->d_hres = hb_at<HostResult>(db, HB_RES);
-        c->h_spec = hb_at<SpecState>(hb, HB_SPEC); c->d_hspec = hb_at<SpecState>(db, HB_SPEC);
-        c->h_th = hb_at<TickHeader>(hb, HB_TICK); c->d_hth = hb_at<TickHeader>(db, HB_TICK);
-        c->h_ranges = hb_at<InstanceRange>(hb, HB_RANGES); c->d_hranges = hb_at<InstanceRange>(db, HB_RANGES);
-    }
+    c->nslots_cap = std::max(2u * c->nslots, 1024u);                               // head-room: entities added later may bring new (ModelId, sortable) groups
+    HIPCHK(c, c->carve(c->nslots_cap));
     HIPCHK(c, c->d_spec.alloc(1, nullptr)); HIPCHK(c, hipMemset(c->d_spec.p, 0, sizeof(SpecState)));
     HIPCHK(c, hipMemsetAsync(c->d_hdr.p, 0, NUM_FRAME_HEADERS * sizeof(FrameHeader), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_th.p, 0, sizeof(TickHeader), c->stream));
@@ -1333,25 +1293,14 @@ static int ensure_second_lane(re_ctx *c) {
     HIPCHK(c, k.d_cell_stamp.alloc(std::max<size_t>(c->d_cell_stamp.n, 1), acct)); HIPCHK(c, k.d_params.alloc(1, acct));
     HIPCHK(c, hipMemset(k.d_hdr.p, 0, NUM_FRAME_HEADERS * sizeof(FrameHeader))); HIPCHK(c, hipMemset(k.d_item_row.p, 0, (size_t)c->item_cap * 8)); HIPCHK(c, hipMemset(k.d_item_slot.p, 0xFF, (size_t)c->item_cap * 8));
     HIPCHK(c, hipMemset(k.d_cell_stamp.p, 0, k.d_cell_stamp.n * 4));
-    {
-        void *hb = nullptr, *db = nullptr;
-        HIPCHK(c, alloc_host_block(c->nslots_cap, &hb, &db));
-        k.h_block = hb;
-        k.h_res = hb_at<HostResult>(hb, HB_RES); k.d_hres = hb_at<HostResult>(db, HB_RES);
-        k.h_ranges = hb_at<InstanceRange>(hb, HB_RANGES); k.d_hranges = hb_at<InstanceRange>(db, HB_RANGES);
-    }
-    k.deferred_pack = false; k.lane_seq = 0; k.busy = false;
+    HIPCHK(c, k.carve(c->nslots_cap));
     c->park_ready = true;
     return RE_OK;
 }
 static void free_second_lane(re_ctx *c) {
     if (c->lane_id) switch_lane(c);                                          // lane 0 is the one the rest of the context owns
-    re_ctx::LanePark &k = c->park; uint64_t *acct = &c->dev_bytes;
-    if (k.stream) { (void)sync_stream(k.stream); (void)hipStreamDestroy(k.stream); k.stream = nullptr; }
-    k.d_hdr.release(acct); k.d_item_row.release(acct); k.d_item_slot.release(acct); k.d_out_ids.release(acct); k.d_out_mats.release(acct); k.d_cell_stamp.release(acct); k.d_params.release(acct);
-    if (k.h_block) { (void)hipHostFree(k.h_block); k.h_block = nullptr; }
-    k.h_res = nullptr; k.d_hres = nullptr; k.h_ranges = nullptr; k.d_hranges = nullptr;
-    k.deferred_pack = false; k.busy = false; c->park_ready = false;
+    if (c->park.stream) { (void)sync_stream(c->park.stream); (void)hipStreamDestroy(c->park.stream); }
+    c->park = re_ctx::LanePark{}; c->park_ready = false;
 }
 // Everything except the alternating frames themselves works on one lane: send the other lane's pending pack off and wait for its stream.
 // The current lane holds the newest frame (lanes are switched before a frame is issued), so results, stamps and frame parameters
@@ -1896,21 +1845,20 @@ static int sync_mirrors(re_ctx *c) {
     std::sort(c->stale_slots.begin(), c->stale_slots.end()); c->stale_slots.erase(std::unique(c->stale_slots.begin(), c->stale_slots.end()), c->stale_slots.end());
     const uint32_t n = (uint32_t)c->stale_slots.size();
     DevBuf<uint32_t> d_slots, d_hdr, d_offs, d_rows; DevBuf<uint64_t> d_keys;
-    auto done = [&](int rc) { d_slots.release(nullptr); d_hdr.release(nullptr); d_offs.release(nullptr); d_rows.release(nullptr); d_keys.release(nullptr); return rc; };
-    if (d_slots.alloc(n, nullptr) != hipSuccess || d_hdr.alloc((size_t)n * 4, nullptr) != hipSuccess || d_offs.alloc((size_t)n + 1, nullptr) != hipSuccess || d_keys.alloc(n, nullptr) != hipSuccess) return done(c->fail(RE_E_HIP, "sync_mirrors: out of device memory"));
+    if (d_slots.alloc(n, nullptr) != hipSuccess || d_hdr.alloc((size_t)n * 4, nullptr) != hipSuccess || d_offs.alloc((size_t)n + 1, nullptr) != hipSuccess || d_keys.alloc(n, nullptr) != hipSuccess) return c->fail(RE_E_HIP, "sync_mirrors: out of device memory");
     std::vector<uint64_t> keys(n); std::vector<uint32_t> hdr((size_t)n * 4), offs((size_t)n + 1, 0);
-    if (hipMemcpyAsync(d_slots.p, c->stale_slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, st) != hipSuccess) return done(c->fail(RE_E_HIP, "sync_mirrors: copy"));
+    if (hipMemcpyAsync(d_slots.p, c->stale_slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, st) != hipSuccess) return c->fail(RE_E_HIP, "sync_mirrors: copy");
     hipLaunchKernelGGL(k_rb_gather_cells, dim3((n + 255) / 256), dim3(256), 0, st, n, d_slots.p, rb_cells(c), d_keys.p, d_hdr.p);
     (void)hipMemcpyAsync(keys.data(), d_keys.p, (size_t)n * 8, hipMemcpyDeviceToHost, st); (void)hipMemcpyAsync(hdr.data(), d_hdr.p, (size_t)n * 16, hipMemcpyDeviceToHost, st);
-    if (sync_stream(st) != hipSuccess) return done(c->fail(RE_E_HIP, "sync_mirrors: section headers"));
+    if (sync_stream(st) != hipSuccess) return c->fail(RE_E_HIP, "sync_mirrors: section headers");
     for (uint32_t i = 0; i < n; i++) offs[i + 1] = offs[i] + hdr[(size_t)i * 4 + 2] + hdr[(size_t)i * 4 + 3];
     std::vector<uint32_t> rows(std::max<uint32_t>(offs[n], 1u));
     if (offs[n]) {
-        if (d_rows.alloc(offs[n], nullptr) != hipSuccess) return done(c->fail(RE_E_HIP, "sync_mirrors: out of device memory"));
+        if (d_rows.alloc(offs[n], nullptr) != hipSuccess) return c->fail(RE_E_HIP, "sync_mirrors: out of device memory");
         (void)hipMemcpyAsync(d_offs.p, offs.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice, st);
         hipLaunchKernelGGL(k_rb_gather_rows, dim3((n + 255) / 256), dim3(256), 0, st, n, d_slots.p, d_offs.p, rb_cells(c), d_rows.p);
         (void)hipMemcpyAsync(rows.data(), d_rows.p, (size_t)offs[n] * 4, hipMemcpyDeviceToHost, st);
-        if (sync_stream(st) != hipSuccess) return done(c->fail(RE_E_HIP, "sync_mirrors: section rows"));
+        if (sync_stream(st) != hipSuccess) return c->fail(RE_E_HIP, "sync_mirrors: section rows");
     }
     auto is_pad = [](uint64_t k) { return (k & 0xFFFFFFFFFFFFull) == 0xFFFFFFFFFFFFull; };
     for (uint32_t i = 0; i < n; i++) {
@@ -1932,7 +1880,7 @@ static int sync_mirrors(re_ctx *c) {
         }
     }
     c->stale_slots.clear();
-    return done(RE_OK);
+    return RE_OK;
 }
 // the shared world sections the device created, changed or retired (rebucket_on_device2): ids, counts, linked slots, members
 static int sync_shared_mirrors(re_ctx *c) {
@@ -1943,23 +1891,22 @@ static int sync_shared_mirrors(re_ctx *c) {
     std::sort(c->stale_shared.begin(), c->stale_shared.end()); c->stale_shared.erase(std::unique(c->stale_shared.begin(), c->stale_shared.end()), c->stale_shared.end());
     const uint32_t n = (uint32_t)c->stale_shared.size();
     DevBuf<uint32_t> d_idx, d_hdr, d_offs, d_rows; DevBuf<uint64_t> d_keys; DevBuf<int32_t> d_cells;
-    auto done = [&](int rc) { d_idx.release(nullptr); d_hdr.release(nullptr); d_offs.release(nullptr); d_rows.release(nullptr); d_keys.release(nullptr); d_cells.release(nullptr); return rc; };
     if (d_idx.alloc(n, nullptr) != hipSuccess || d_hdr.alloc((size_t)n * 5, nullptr) != hipSuccess || d_offs.alloc((size_t)n + 1, nullptr) != hipSuccess || d_keys.alloc((size_t)n * 8, nullptr) != hipSuccess
-        || d_cells.alloc((size_t)n * 8, nullptr) != hipSuccess) return done(c->fail(RE_E_HIP, "sync_mirrors: out of device memory"));
+        || d_cells.alloc((size_t)n * 8, nullptr) != hipSuccess) return c->fail(RE_E_HIP, "sync_mirrors: out of device memory");
     std::vector<uint64_t> keys((size_t)n * 8); std::vector<uint32_t> hdr((size_t)n * 5), offs((size_t)n + 1, 0); std::vector<int32_t> cells((size_t)n * 8);
-    if (hipMemcpyAsync(d_idx.p, c->stale_shared.data(), (size_t)n * 4, hipMemcpyHostToDevice, st) != hipSuccess) return done(c->fail(RE_E_HIP, "sync_mirrors: copy"));
+    if (hipMemcpyAsync(d_idx.p, c->stale_shared.data(), (size_t)n * 4, hipMemcpyHostToDevice, st) != hipSuccess) return c->fail(RE_E_HIP, "sync_mirrors: copy");
     hipLaunchKernelGGL(k_rb2_gather_shared, dim3((n + 255) / 256), dim3(256), 0, st, n, (const uint32_t *)d_idx.p, sh_table(c), d_keys.p, d_hdr.p, d_cells.p);
     (void)hipMemcpyAsync(keys.data(), d_keys.p, (size_t)n * 64, hipMemcpyDeviceToHost, st); (void)hipMemcpyAsync(hdr.data(), d_hdr.p, (size_t)n * 20, hipMemcpyDeviceToHost, st);
     (void)hipMemcpyAsync(cells.data(), d_cells.p, (size_t)n * 32, hipMemcpyDeviceToHost, st);
-    if (sync_stream(st) != hipSuccess) return done(c->fail(RE_E_HIP, "sync_mirrors: shared section headers"));
+    if (sync_stream(st) != hipSuccess) return c->fail(RE_E_HIP, "sync_mirrors: shared section headers");
     for (uint32_t i = 0; i < n; i++) offs[i + 1] = offs[i] + hdr[(size_t)i * 5 + 2] + hdr[(size_t)i * 5 + 3];
     std::vector<uint32_t> rows(std::max<uint32_t>(offs[n], 1u));
     if (offs[n]) {
-        if (d_rows.alloc(offs[n], nullptr) != hipSuccess) return done(c->fail(RE_E_HIP, "sync_mirrors: out of device memory"));
+        if (d_rows.alloc(offs[n], nullptr) != hipSuccess) return c->fail(RE_E_HIP, "sync_mirrors: out of device memory");
         (void)hipMemcpyAsync(d_offs.p, offs.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice, st);
         hipLaunchKernelGGL(k_rb2_gather_shared_rows, dim3((n + 255) / 256), dim3(256), 0, st, n, (const uint32_t *)d_idx.p, (const uint32_t *)d_offs.p, sh_table(c), (const uint32_t *)c->d_rows.p, d_rows.p);
         (void)hipMemcpyAsync(rows.data(), d_rows.p, (size_t)offs[n] * 4, hipMemcpyDeviceToHost, st);
-        if (sync_stream(st) != hipSuccess) return done(c->fail(RE_E_HIP, "sync_mirrors: shared section rows"));
+        if (sync_stream(st) != hipSuccess) return c->fail(RE_E_HIP, "sync_mirrors: shared section rows");
     }
     for (uint32_t i = 0; i < n; i++) {
         const uint32_t s2 = c->stale_shared[i];
@@ -1982,7 +1929,7 @@ static int sync_shared_mirrors(re_ctx *c) {
         }
     }
     c->stale_shared.clear();
-    return done(RE_OK);
+    return RE_OK;
 }
 
 static bool device_rebucket_applicable(const re_ctx *c) {
@@ -2088,13 +2035,11 @@ static int rebucket_on_device2(re_ctx *c, uint32_t M, std::vector<uint32_t> *hos
             auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
             const size_t o_seq = up(sizeof(Rb2Status)), o_off = o_seq + 256, o_fu = o_off + up(MAX_LEVELS * 4), o_fs = o_fu + up((size_t)oc * 4), o_keep = o_fs + up((size_t)2 * mc * 4),
                          o_su = o_keep + up((size_t)mc * 4), o_ss = o_su + up((size_t)oc * sizeof(Rb2Seg)), total = o_ss + up((size_t)2 * mc * sizeof(Rb2ShSeg));
-            if (B.pin) { (void)hipHostFree(B.pin); B.pin = nullptr; }
-            void *hp = nullptr, *dp = nullptr; HIPCHK(c, hipHostMalloc(&hp, total, hipHostMallocMapped)); HIPCHK(c, hipHostGetDevicePointer(&dp, hp, 0));
-            B.pin = static_cast<uint8_t *>(hp); B.d_pin = static_cast<uint8_t *>(dp); B.pin_bytes = total;
-            B.h_status = reinterpret_cast<Rb2Status *>(B.pin); B.d_h_status = reinterpret_cast<Rb2Status *>(dp);
-            B.h_seq = reinterpret_cast<uint32_t *>(B.pin + o_seq); B.d_h_seq = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(dp) + o_seq); *B.h_seq = 0; B.seq = 0; B.h_free_off = reinterpret_cast<uint32_t *>(B.pin + o_off); B.h_free_u = reinterpret_cast<uint32_t *>(B.pin + o_fu);
-            B.h_free_s = reinterpret_cast<uint32_t *>(B.pin + o_fs); B.h_keep = reinterpret_cast<uint32_t *>(B.pin + o_keep);
-            B.h_segs_u = reinterpret_cast<Rb2Seg *>(B.pin + o_su); B.h_segs_s = reinterpret_cast<Rb2ShSeg *>(B.pin + o_ss);
+            HIPCHK(c, B.pin.alloc(total, hipHostMallocMapped));
+            B.h_status = B.pin.host<Rb2Status>(); B.d_h_status = B.pin.dev<Rb2Status>();
+            B.h_seq = B.pin.host<uint32_t>(o_seq); B.d_h_seq = B.pin.dev<uint32_t>(o_seq); B.seq = 0; B.h_free_off = B.pin.host<uint32_t>(o_off); B.h_free_u = B.pin.host<uint32_t>(o_fu);
+            B.h_free_s = B.pin.host<uint32_t>(o_fs); B.h_keep = B.pin.host<uint32_t>(o_keep);
+            B.h_segs_u = B.pin.host<Rb2Seg>(o_su); B.h_segs_s = B.pin.host<Rb2ShSeg>(o_ss);
         }
         B.cap = mc;
     }
@@ -2102,7 +2047,7 @@ static int rebucket_on_device2(re_ctx *c, uint32_t M, std::vector<uint32_t> *hos
     Rb2Status &hs = *B.h_status; hs = Rb2Status{}; hs.pool_used = c->pool_used;
     if (!(B.status_clean && B.status_pool == c->pool_used)) HIPCHK(c, hipMemcpyAsync(B.status.p, &hs, sizeof hs, hipMemcpyHostToDevice, st));      // (else: the last batch's final read-back left the block ready)
     B.status_clean = false;
-    auto mapped = [&](const void *h) { return reinterpret_cast<uint32_t *>(B.d_pin + (reinterpret_cast<const uint8_t *>(h) - B.pin)); };
+    auto mapped = [&](const void *h) { return B.pin.dev<uint32_t>(static_cast<const char *>(h) - B.pin.host<char>()); };
     const RbTables T = rb_tables(c); const RbCells C = rb_cells(c); const ShTable S = sh_table(c);
     // the status block as the kernels so far left it: published into the mapped block by one small kernel and polled (a copy plus a stream synchronise costs ~15 us more, three times a batch)
     auto wait_status = [&](uint32_t seq) -> int {
@@ -2640,9 +2585,8 @@ template <typename T> static hipError_t grow_buf(DevBuf<T> &b, size_t keep, size
     DevBuf<T> nb; hipError_t e = nb.alloc(count, acct);
     if (e != hipSuccess) return e;
     if (keep && b.p) { e = hipMemcpyAsync(nb.p, b.p, keep * sizeof(T), hipMemcpyDeviceToDevice, st); if (e == hipSuccess) e = sync_stream(st); }
-    if (e != hipSuccess) { nb.release(acct); return e; }
-    b.release(acct); b = nb;
-    return hipSuccess;
+    if (e == hipSuccess) b = std::move(nb);
+    return e;
 }
 // per-frame buffers whose size follows the number of rows: instance lists, packed output (when the caller gave no capacity), mover / out-of-bounds lists
 static int size_frame_buffers(re_ctx *c) {
@@ -2683,7 +2627,7 @@ static int ensure_row_capacity(re_ctx *c, uint32_t need) {
             HIPCHK(c, hipMemcpyAsync(nmat.p + (size_t)new_cap * 16, c->d_mat.p + (size_t)old_cap * 16, (size_t)c->n_ghost * 64, hipMemcpyDeviceToDevice, st));
         }
         HIPCHK(c, sync_stream(st));
-        c->d_id.release(a); c->d_mat.release(a); c->d_id = nid; c->d_mat = nmat;
+        c->d_id = std::move(nid); c->d_mat = std::move(nmat);
     }
     if (c->n_ghost) {                                                        // the row pool names ghost instances by row: they moved up with the capacity
         const uint32_t delta = new_cap - old_cap;
@@ -2743,23 +2687,17 @@ static int regrow_groups(re_ctx *c) {
     HIPCHK(c, hipMemcpy(c->d_gc_model.p, gm.data(), (size_t)c->ngclass * 4, hipMemcpyHostToDevice)); HIPCHK(c, hipMemcpy(c->d_gc_rs.p, gr.data(), (size_t)c->ngclass * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->d_gc_sort.p, gs.data(), (size_t)c->ngclass * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemset(c->d_group_count.p, 0, (size_t)std::max(c->nslots, 1u) * 4)); HIPCHK(c, hipMemset(c->d_group_fill.p, 0, (size_t)std::max(c->nslots, 1u) * 4));
-    c->d_gcount.release(acct); c->d_gfill.release(acct); c->gc_dirty[0] = c->gc_dirty[1] = false;
+    c->d_gcount.release(); c->d_gfill.release(); c->gc_dirty[0] = c->gc_dirty[1] = false;      // (a table of more than COUNT_SLOTS_MAX slots has none)
     if (c->nslots <= COUNT_SLOTS_MAX) {
         const size_t words = 2u * CURSOR_SHARDS * (size_t)std::max(c->nslots, 1u);
         HIPCHK(c, c->d_gcount.alloc(words, acct)); HIPCHK(c, c->d_gfill.alloc(words, acct));
         HIPCHK(c, hipMemset(c->d_gcount.p, 0, words * 4)); HIPCHK(c, hipMemset(c->d_gfill.p, 0, words * 4));
     }
     if (c->nslots > c->nslots_cap) {                                        // the InstanceRange table of the result block
-        void *hb = nullptr, *db = nullptr;
-        const uint32_t cap = std::max(2u * c->nslots, 1024u);
-        HIPCHK(c, alloc_host_block(cap, &hb, &db));
-        memcpy(hb, c->h_block, HB_RANGES);                                  // frame result, speculation word, tick counters as they are
-        (void)hipHostFree(c->h_block);
-        c->h_block = hb; c->nslots_cap = cap;
-        c->h_res = hb_at<HostResult>(hb, HB_RES); c->d_hres = hb_at<HostResult>(db, HB_RES);
-        c->h_spec = hb_at<SpecState>(hb, HB_SPEC); c->d_hspec = hb_at<SpecState>(db, HB_SPEC);
-        c->h_th = hb_at<TickHeader>(hb, HB_TICK); c->d_hth = hb_at<TickHeader>(db, HB_TICK);
-        c->h_ranges = hb_at<InstanceRange>(hb, HB_RANGES); c->d_hranges = hb_at<InstanceRange>(db, HB_RANGES);
+        HostBlock nb; const uint32_t cap = std::max(2u * c->nslots, 1024u);
+        HIPCHK(c, nb.carve(cap));
+        memcpy(nb.h_block.h, c->h_block.h, HB_RANGES);                      // frame result, speculation word, tick counters as they are
+        static_cast<HostBlock &>(*c) = std::move(nb); c->nslots_cap = cap;
     }
     c->last_pack.kind = 0;
     return upload_lod_tables(c);
@@ -2809,21 +2747,20 @@ static int create_rows(re_ctx *c, const re_entities *E, const std::vector<NewRow
     HIPCHK(c, hipMemcpyAsync(c->d_orig.p + row0, orig.data(), (size_t)m * 24, hipMemcpyHostToDevice, st));
     // TRS -> matrix, AABB, section decision: the upload's kernel over the new rows
     DevBuf<uint64_t> d_key; DevBuf<uint8_t> d_nk; DevBuf<SharedRec> d_sr; DevBuf<uint32_t> d_cnt;
-    auto done = [&](int rc) { d_key.release(nullptr); d_nk.release(nullptr); d_sr.release(nullptr); d_cnt.release(nullptr); return rc; };
-    if (d_key.alloc(m, nullptr) != hipSuccess || d_nk.alloc(m, nullptr) != hipSuccess || d_sr.alloc(m, nullptr) != hipSuccess || d_cnt.alloc(4, nullptr) != hipSuccess) return done(c->fail(RE_E_HIP, "create_rows: out of device memory"));
+    if (d_key.alloc(m, nullptr) != hipSuccess || d_nk.alloc(m, nullptr) != hipSuccess || d_sr.alloc(m, nullptr) != hipSuccess || d_cnt.alloc(4, nullptr) != hipSuccess) return c->fail(RE_E_HIP, "create_rows: out of device memory");
     (void)hipMemsetAsync(d_cnt.p, 0, 16, st);
     hipLaunchKernelGGL(k_transform_assign, dim3((m + 255) / 256), dim3(256), 0, st, row_arrays(c), row0, m, c->cfg.outline_length, c->cfg.atomic_length, d_key.p, d_nk.p, d_sr.p, d_cnt.p, m);
     (void)hipMemsetAsync(c->d_row_cell.p + row0, 0xFF, (size_t)m * 4, st);      // ROW_CELL_NONE: in no section yet (the device-side re-bucket reads it; rows beyond the upload were never written)
     std::vector<uint64_t> key(m); std::vector<uint8_t> nk(m); uint32_t nsr = 0;
     (void)hipMemcpyAsync(key.data(), d_key.p, (size_t)m * 8, hipMemcpyDeviceToHost, st); (void)hipMemcpyAsync(nk.data(), d_nk.p, m, hipMemcpyDeviceToHost, st); (void)hipMemcpyAsync(&nsr, d_cnt.p, 4, hipMemcpyDeviceToHost, st);
-    if (hipGetLastError() != hipSuccess || sync_stream(st) != hipSuccess) return done(c->fail(RE_E_HIP, "create_rows: kernel / copy failed"));
+    if (hipGetLastError() != hipSuccess || sync_stream(st) != hipSuccess) return c->fail(RE_E_HIP, "create_rows: kernel / copy failed");
     std::vector<SharedRec> sr(std::min(nsr, m));
-    if (!sr.empty() && hipMemcpy(sr.data(), d_sr.p, sr.size() * sizeof(SharedRec), hipMemcpyDeviceToHost) != hipSuccess) return done(c->fail(RE_E_HIP, "create_rows: copy failed"));
+    if (!sr.empty() && hipMemcpy(sr.data(), d_sr.p, sr.size() * sizeof(SharedRec), hipMemcpyDeviceToHost) != hipSuccess) return c->fail(RE_E_HIP, "create_rows: copy failed");
     // the dynamic table
     for (const Dyn &d : dyn) {
-        uint32_t j = 0; int rc = alloc_dyn_slot(c, row0 + d.k, &j); if (rc != RE_OK) return done(rc);
+        uint32_t j = 0; int rc = alloc_dyn_slot(c, row0 + d.k, &j); if (rc != RE_OK) return rc;
         if (hipMemcpy(c->d_dyn_vel.p + (size_t)j * 3, d.v, 12, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(c->d_dyn_acc.p + (size_t)j * 3, d.a, 12, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(c->d_dyn_rotvel.p + (size_t)j * 4, d.rv, 16, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(c->d_dyn_rotacc.p + (size_t)j * 4, d.ra, 16, hipMemcpyHostToDevice) != hipSuccess) return done(c->fail(RE_E_HIP, "create_rows: copy failed"));
+            hipMemcpy(c->d_dyn_rotvel.p + (size_t)j * 4, d.rv, 16, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(c->d_dyn_rotacc.p + (size_t)j * 4, d.ra, 16, hipMemcpyHostToDevice) != hipSuccess) return c->fail(RE_E_HIP, "create_rows: copy failed");
     }
     // host mirrors
     uint32_t rejected = 0;
@@ -2843,7 +2780,7 @@ static int create_rows(re_ctx *c, const re_entities *E, const std::vector<NewRow
     for (const SharedRec &q : sr) { auto it = c->add_keys.find(q.row); if (it != c->add_keys.end()) memcpy(it->second.keys, q.keys, sizeof q.keys); }
     c->n += m;
     if (n_rejected) *n_rejected = rejected;
-    return done(RE_OK);
+    return RE_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3017,10 +2954,10 @@ static int apply_changes_impl(re_ctx *c, const re_change *changes, uint32_t n, c
     if (!ghosts.empty()) {
         std::vector<Pair32> cl; cl.reserve(ghosts.size());
         for (auto &g : ghosts) { const uint32_t gr = c->ghost_base + c->n_ghost++; cl.push_back(Pair32{ g.first, gr }); c->h_ghost_gc.push_back(c->h_gclass[g.first]); c->ghost_map[g.second].push_back(gr); ghost_touched.insert(g.second); }
-        Pair32 *d = nullptr; HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&d), cl.size() * sizeof(Pair32)));
-        HIPCHK(c, hipMemcpyAsync(d, cl.data(), cl.size() * sizeof(Pair32), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_clone_rows, dim3(((uint32_t)cl.size() * 4u + 255) / 256), dim3(256), 0, st, (uint32_t)cl.size(), d, c->d_id.p, c->d_mat.p);   // before any component write of this batch
-        HIPCHK(c, sync_stream(st)); (void)hipFree(d);
+        DevBuf<Pair32> d; HIPCHK(c, d.alloc(cl.size(), nullptr));
+        HIPCHK(c, hipMemcpyAsync(d.p, cl.data(), cl.size() * sizeof(Pair32), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_clone_rows, dim3(((uint32_t)cl.size() * 4u + 255) / 256), dim3(256), 0, st, (uint32_t)cl.size(), d.p, c->d_id.p, c->d_mat.p);   // before any component write of this batch
+        HIPCHK(c, sync_stream(st));
     }
     // ---- the entities this batch adds: rows, columns, matrices, section decisions (the tree sees them in rebucket(): TreeOp kind 4, in list order)
     if (!new_rows.empty()) { int rc = create_rows(c, added, new_rows, nullptr); if (rc != RE_OK) return rc; }
@@ -3073,18 +3010,13 @@ static int apply_changes_impl(re_ctx *c, const re_change *changes, uint32_t n, c
     static const bool no_small = getenv("RE_EXP_NO_APPLY_SMALL") != nullptr;      // A/B switch of tools/change_cost.py
     if ((!ops.empty() || !list.empty()) && ops.size() <= APPLY_SMALL_MAX && list.size() <= APPLY_SMALL_MAX && c->h_th && !no_small) {
         // the common small batch: ONE launch that reads its input from a mapped staging block and publishes the counters (k_apply_small)
-        if (!c->h_chg) {
-            void *hp = nullptr, *dp = nullptr;
-            HIPCHK(c, hipHostMalloc(&hp, APPLY_SMALL_MAX * (sizeof(WriteOp) + 4u), hipHostMallocMapped));
-            HIPCHK(c, hipHostGetDevicePointer(&dp, hp, 0));
-            c->h_chg = static_cast<uint8_t *>(hp); c->d_chg = static_cast<uint8_t *>(dp);
-        }
-        if (!ops.empty()) memcpy(c->h_chg, ops.data(), ops.size() * sizeof(WriteOp));
-        if (!list.empty()) memcpy(c->h_chg + APPLY_SMALL_MAX * sizeof(WriteOp), list.data(), list.size() * 4);
+        if (!c->chg.h) HIPCHK(c, c->chg.alloc(APPLY_SMALL_MAX * (sizeof(WriteOp) + 4u), hipHostMallocMapped));
+        if (!ops.empty()) memcpy(c->chg.h, ops.data(), ops.size() * sizeof(WriteOp));
+        if (!list.empty()) memcpy(c->chg.host<char>(APPLY_SMALL_MAX * sizeof(WriteOp)), list.data(), list.size() * 4);
         std::atomic_thread_fence(std::memory_order_release);
         const uint32_t seq = ++c->tick_seq;
-        hipLaunchKernelGGL(k_apply_small, dim3(1), dim3(256), 0, st, (uint32_t)ops.size(), reinterpret_cast<const WriteOp *>(c->d_chg), (uint32_t)list.size(),
-                           reinterpret_cast<const uint32_t *>(c->d_chg + APPLY_SMALL_MAX * sizeof(WriteOp)), row_arrays(c), c->d_dyn_vel.p, c->d_dyn_acc.p, c->d_dyn_rotvel.p, c->d_dyn_rotacc.p,
+        hipLaunchKernelGGL(k_apply_small, dim3(1), dim3(256), 0, st, (uint32_t)ops.size(), c->chg.dev<const WriteOp>(), (uint32_t)list.size(),
+                           c->chg.dev<const uint32_t>(APPLY_SMALL_MAX * sizeof(WriteOp)), row_arrays(c), c->d_dyn_vel.p, c->d_dyn_acc.p, c->d_dyn_rotvel.p, c->d_dyn_rotacc.p,
                            c->d_row_cell.p, c->d_cell_key.p, c->d_sh_cells.p, c->cfg.outline_length, c->cfg.atomic_length, c->d_th.p, c->d_movers.p, c->d_oob.p, c->list_cap, c->d_hth, seq);
         HIPCHK(c, hipGetLastError());
         const volatile TickHeader *t = c->h_th;
@@ -3212,8 +3144,7 @@ extern "C" int re_collide(re_ctx *c, uint32_t flags, re_collision *pairs, uint32
     if (!c->d_col_hdr.p) {
         HIPCHK(c, c->d_col_hdr.alloc(1, nullptr)); HIPCHK(c, c->d_col_region.alloc(COL_REGION_CAP, nullptr)); HIPCHK(c, c->d_col_high.alloc(COL_REGION_CAP, nullptr));
         HIPCHK(c, c->d_col_shared.alloc(COL_SHARED_CAP, nullptr)); HIPCHK(c, c->d_col_near.alloc(COL_REGION_CAP, nullptr));
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_col), sizeof(ColHeader), hipHostMallocMapped | hipHostMallocCoherent)); memset(c->h_col, 0, sizeof(ColHeader));
-        HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&c->d_hcol), c->h_col, 0));
+        HIPCHK(c, c->col_pub.alloc(sizeof(ColHeader), hipHostMallocMapped | hipHostMallocCoherent)); c->h_col = c->col_pub.host<ColHeader>(); c->d_hcol = c->col_pub.dev<ColHeader>();
     }
     if (!c->col_moved_cap) {
         // by the capacities, not the counts in use: rows and dynamic slots are added within the slack of ensure_row_capacity /
@@ -3226,7 +3157,7 @@ extern "C" int re_collide(re_ctx *c, uint32_t flags, re_collision *pairs, uint32
         HIPCHK(c, hipMemsetAsync(c->d_row_moved.p, 0, c->col_rows, c->stream)); HIPCHK(c, hipMemsetAsync(c->d_col_tab.p, 0xFF, (size_t)c->col_tab_size * 16, c->stream));
     }
     const uint32_t want = std::max(capacity, 1u << 12);
-    if (want > c->col_pair_cap) { c->d_col_pairs.release(nullptr); HIPCHK(c, c->d_col_pairs.alloc(want, nullptr)); c->col_pair_cap = want; }
+    if (want > c->col_pair_cap) { HIPCHK(c, c->d_col_pairs.alloc(want, nullptr)); c->col_pair_cap = want; }
     HIPCHK(c, hipMemsetAsync(c->d_col_hdr.p, 0, sizeof(ColHeader), st));
     unsigned long long *tab_key = c->d_col_tab.p, *tab_min = c->d_col_tab.p + c->col_tab_size;
     const uint32_t user_cell = c->user_row != ROW_CELL_NONE ? c->h_row_cell[c->user_row] : ROW_CELL_NONE;
@@ -3318,10 +3249,7 @@ static bool load() {
 static void comm_release(re_ctx *c) {
     re_ctx::Comm &m = c->comm;
     if (m.comm && m.owned && rccl::CommDestroy) (void)rccl::CommDestroy(reinterpret_cast<rccl::ncclComm_t>(m.comm));
-    for (int b = 0; b < 2; b++) { m.slab[b].release(&c->dev_bytes); m.recv[b].release(&c->dev_bytes); }
-    m.big_ids.release(&c->dev_bytes); m.big_mats.release(&c->dev_bytes);
-    if (m.h_hdr) (void)hipHostFree(m.h_hdr);
-    m = re_ctx::Comm{};
+    m = re_ctx::Comm{};                                                     // (frees the slabs, the receive buffers and the header block)
     c->ext_out_ids = nullptr; c->ext_out_mats = nullptr; c->ext_out_cap = 0; c->ext_out_count = nullptr;
 }
 static int comm_setup(re_ctx *c, void *comm, bool owned, int rank, int n_ranks, uint32_t slab_instances) {
@@ -3332,9 +3260,7 @@ static int comm_setup(re_ctx *c, void *comm, bool owned, int rank, int n_ranks, 
         HIPCHK(c, m.slab[b].alloc(m.words, &c->dev_bytes)); HIPCHK(c, m.recv[b].alloc((size_t)m.words * n_ranks, &c->dev_bytes));
         HIPCHK(c, hipMemset(m.slab[b].p, 0, (size_t)m.words * 4)); HIPCHK(c, hipMemset(m.recv[b].p, 0, (size_t)m.words * n_ranks * 4));
     }
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&m.h_hdr), ((size_t)n_ranks * 4 + 32) * 4, hipHostMallocMapped | hipHostMallocCoherent));
-    memset(m.h_hdr, 0, ((size_t)n_ranks * 4 + 32) * 4);
-    HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void **>(&m.d_hhdr), m.h_hdr, 0));
+    HIPCHK(c, m.hdr_pub.alloc(((size_t)n_ranks * 4 + 32) * 4, hipHostMallocMapped | hipHostMallocCoherent)); m.h_hdr = m.hdr_pub.host<uint32_t>(); m.d_hhdr = m.hdr_pub.dev<uint32_t>();
     m.counts.assign(n_ranks, 0u); m.seq = 0; m.last = -1; m.pending = -1; m.hdr_seq = 0;
     return RE_OK;
 }
@@ -3438,7 +3364,6 @@ static int gather_finish(re_ctx *c, re_gathered *out) {
     if (max_total > c->out_cap) return c->fail(RE_E_CAPACITY, "re_allgather_visible: a rank packed %u instances, more than this rank's output buffer holds (%u)", max_total, c->out_cap);
     { int rc = repack_last_frame(c, c->d_out_ids.p, c->d_out_mats.p, c->out_cap); if (rc != RE_OK) return rc; }
     if (m.big_cap < max_total) {
-        m.big_ids.release(&c->dev_bytes); m.big_mats.release(&c->dev_bytes);
         m.big_cap = max_total + max_total / 4u;
         HIPCHK(c, m.big_ids.alloc((size_t)m.big_cap * m.n, &c->dev_bytes)); HIPCHK(c, m.big_mats.alloc((size_t)m.big_cap * m.n * 16, &c->dev_bytes));
     }
@@ -3515,19 +3440,18 @@ extern "C" int re_export_entities(re_ctx *c, const uint32_t *ids, uint32_t n, re
         uint32_t j = 0; slots[i] = c->dyn_index(rows[i], j) ? j : 0xFFFFFFFFu;
     }
     DevBuf<uint32_t> d_rows, d_slots; DevBuf<ExportRec> d_out;
-    auto done = [&](int rc) { d_rows.release(nullptr); d_slots.release(nullptr); d_out.release(nullptr); return rc; };
-    if (d_rows.alloc(n, nullptr) != hipSuccess || d_slots.alloc(n, nullptr) != hipSuccess || d_out.alloc(n, nullptr) != hipSuccess) return done(c->fail(RE_E_HIP, "re_export_entities: out of device memory"));
+    if (d_rows.alloc(n, nullptr) != hipSuccess || d_slots.alloc(n, nullptr) != hipSuccess || d_out.alloc(n, nullptr) != hipSuccess) return c->fail(RE_E_HIP, "re_export_entities: out of device memory");
     hipStream_t st = c->stream;
     (void)hipMemcpyAsync(d_rows.p, rows.data(), (size_t)n * 4, hipMemcpyHostToDevice, st); (void)hipMemcpyAsync(d_slots.p, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, st);
     hipLaunchKernelGGL(k_export_rows, dim3((n + 255) / 256), dim3(256), 0, st, n, d_rows.p, d_slots.p, row_arrays(c), c->d_dyn_vel.p, c->d_dyn_acc.p, c->d_dyn_rotvel.p, c->d_dyn_rotacc.p, d_out.p);
     (void)hipMemcpyAsync(out, d_out.p, (size_t)n * sizeof(ExportRec), hipMemcpyDeviceToHost, st);
-    if (hipGetLastError() != hipSuccess || sync_stream(st) != hipSuccess) return done(c->fail(RE_E_HIP, "re_export_entities: kernel / copy failed"));
+    if (hipGetLastError() != hipSuccess || sync_stream(st) != hipSuccess) return c->fail(RE_E_HIP, "re_export_entities: kernel / copy failed");
     for (uint32_t i = 0; i < n; i++) {                                       // what the device rows do not hold: the group's ModelId / sortable index, and the tree's static bit
         const GroupKey &g = c->h_gkeys[c->h_gclass[rows[i]]];
         out[i].model_index = g.model; out[i].render_system = g.rs; out[i].sortable = g.sort;
         out[i].flags = (out[i].flags & ~(F_STATIC | F_DEAD)) | (c->h_flags[rows[i]] & F_STATIC);
     }
-    return done(RE_OK);
+    return RE_OK;
 } RE_ABI_GUARD(c, "re_export_entities")
 
 extern "C" int re_wait(re_ctx *c, re_visible *out_visible, re_tick_result *out_tick) try {
@@ -3832,7 +3756,6 @@ extern "C" int re_ecs_query(re_ctx *c, const int *components, uint32_t n_compone
     HIPCHK(c, hipMemcpyAsync(&cnt, d_cnt.p, 4, hipMemcpyDeviceToHost, c->stream)); HIPCHK(c, sync_stream(c->stream));
     std::vector<uint32_t> found(cnt);
     if (cnt) HIPCHK(c, hipMemcpy(found.data(), d_out.p, (size_t)cnt * 4, hipMemcpyDeviceToHost));
-    d_out.release(nullptr); d_cnt.release(nullptr);
     std::sort(found.begin(), found.end());                                     // BTreeSet<EntityId>: ascending
     for (uint32_t i = 0; i < cnt && i < capacity; i++) ids[i] = found[i];
     if (n_out) *n_out = cnt;
@@ -3943,17 +3866,16 @@ extern "C" int re_debug_get_visible_sections(re_ctx *c, uint32_t capacity, uint6
     HIPCHK(c, hipSetDevice(c->device));
     if (c->cull_inflight) { int rc = finish_cull(c, nullptr); if (rc) return rc; }
     uint32_t cap = std::max(c->ncells, 1u);
-    uint32_t *d_idx = nullptr, *d_cnt = nullptr; uint8_t *d_mult = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&d_idx), (size_t)cap * 4)); HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&d_mult), cap)); HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&d_cnt), 4));
-    HIPCHK(c, hipMemsetAsync(d_cnt, 0, 4, c->stream));
-    if (c->ncells) hipLaunchKernelGGL(k_collect_visible, dim3((c->ncells + 255) / 256), dim3(256), 0, c->stream, c->ncells, c->d_cell_stamp.p, c->frame, d_idx, d_mult, cap, d_cnt);
+    DevBuf<uint32_t> d_idx, d_cnt; DevBuf<uint8_t> d_mult;
+    HIPCHK(c, d_idx.alloc(cap, nullptr)); HIPCHK(c, d_mult.alloc(cap, nullptr)); HIPCHK(c, d_cnt.alloc(1, nullptr));
+    HIPCHK(c, hipMemsetAsync(d_cnt.p, 0, 4, c->stream));
+    if (c->ncells) hipLaunchKernelGGL(k_collect_visible, dim3((c->ncells + 255) / 256), dim3(256), 0, c->stream, c->ncells, c->d_cell_stamp.p, c->frame, d_idx.p, d_mult.p, cap, d_cnt.p);
     uint32_t cnt = 0;
-    HIPCHK(c, hipMemcpyAsync(&cnt, d_cnt, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&cnt, d_cnt.p, 4, hipMemcpyDeviceToHost, c->stream));
     { int rc_ = resolve(c); if (rc_ != RE_OK) return rc_; }
     { int rc_ = sync_mirrors(c); if (rc_ != RE_OK) return rc_; }
     std::vector<uint32_t> idx(cnt); std::vector<uint8_t> mult(cnt);
-    if (cnt) { HIPCHK(c, hipMemcpy(idx.data(), d_idx, (size_t)cnt * 4, hipMemcpyDeviceToHost)); HIPCHK(c, hipMemcpy(mult.data(), d_mult, cnt, hipMemcpyDeviceToHost)); }
-    (void)hipFree(d_idx); (void)hipFree(d_mult); (void)hipFree(d_cnt);
+    if (cnt) { HIPCHK(c, hipMemcpy(idx.data(), d_idx.p, (size_t)cnt * 4, hipMemcpyDeviceToHost)); HIPCHK(c, hipMemcpy(mult.data(), d_mult.p, cnt, hipMemcpyDeviceToHost)); }
     std::vector<uint32_t> order(cnt); for (uint32_t i = 0; i < cnt; i++) order[i] = i;
     std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return c->h_cell_key[idx[a]] < c->h_cell_key[idx[b]]; });
     for (uint32_t i = 0; i < cnt && i < capacity; i++) { if (keys) keys[i] = c->h_cell_key[idx[order[i]]]; if (multiplicity) multiplicity[i] = mult[order[i]]; }
@@ -4163,14 +4085,8 @@ static int run_tree_query(re_ctx *c, const char *call, const char *plural, const
     // the batch, checked whole before anything is touched: built in the pinned buffer that was not the last call's source (a refused batch is never launched:
     // only what this call has built in full is copied to the device)
     const uint32_t k = F.k ^= 1u;
-    if (F.h_cap[k] < n) {
-        if (F.h_q[k]) { (void)hipHostFree(F.h_q[k]); F.h_q[k] = nullptr; F.h_cap[k] = 0; }
-        const size_t cap = std::max<size_t>((size_t)n + n / 2, 256);
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&F.h_q[k]), cap * sizeof(Query), hipHostMallocDefault));
-        F.h_cap[k] = cap;
-    }
-    Query *hq = F.h_q[k];
+    if (F.h_q[k].bytes < n * sizeof(Query)) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, F.h_q[k].alloc(std::max<size_t>((size_t)n + n / 2, 256) * sizeof(Query), hipHostMallocDefault)); }
+    Query *hq = F.h_q[k].template host<Query>();
     for (uint32_t i = 0; i < n; i++) { int rc = build(i, &hq[i]); if (rc != RE_OK) return rc; }
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = settle_frame(c); if (rc != RE_OK) return rc; }                  // (an asynchronous cull or tick in flight is finished first; the query reads no frame stamps)

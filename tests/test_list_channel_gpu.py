@@ -11,6 +11,7 @@ from box_query_rule import box_hits, query_world, draw_boxes
 from test_gpu_parity import build_pair, check_frame, sorted_pairs, assert_clean_publication
 from test_logic_gpu import TYPE_A, TYPE_C, as_tuples, send_types, table_of, types_by_id
 from test_box_query_gpu import ask
+from test_segment_query_gpu import ask as ask_segments
 
 pytestmark = pytest.mark.gpu
 
@@ -178,3 +179,83 @@ def test_flows_across_uploads_and_destroy(R):
         p.close()
         seen.append(totals)
     assert seen[0] == seen[1]
+
+
+def test_context_owns_its_memory(R):
+    """one RE_CFG_PROBE context through everything that allocates lazily, three times over: the blocks of device and pinned memory the library holds
+    (re_debug_live_allocations) are as many after every cycle -- nothing accumulates across uploads --, re_destroy gives back every one of them, the
+    answers of the first cycle are those of the third, and both publication counters stay 0.  (A probe context re-buckets a tick's movers on the host
+    path; the scratch of the device path is covered by the plain context at the end.)"""
+    L, live = R._capi, R._capi.load().re_debug_live_allocations
+    worlds = [query_world(600, 3, 120.0, 64), query_world(1500, 13, 150.0, 64)]
+    static_world = R.synthetic.lattice_world(cells_per_axis=20, first_cell=118)
+    assert not np.any(static_world["flags"] & (R.F_HAS_VEL | R.F_HAS_ROTVEL))
+    cam = R.Camera(*CAM_MIXED)
+    boxes = np.array([[8100, 8300] * 3, [8000, 8192, 8150, 8400, 8192, 8250]], np.float32)
+    p0 = np.array([[8100, 8100, 8100], [8000, 8250, 8192]], np.float32); p1 = np.array([[8300, 8300, 8300], [8400, 8150, 8200]], np.float32)
+
+    def flows(p, ents):
+        """a synchronous frame and every flow behind it; what they answered"""
+        ids = np.ascontiguousarray(ents["id"], np.uint32)
+        p.set_entity_types(ids, np.full(len(ids), TYPE_A, np.uint64))
+        vis = p.cull_and_pack(cam)
+        out = [vis["total"], as_tuples(p.logic_calls()[0]), ask(p, boxes)[0], ask_segments(p, p0, p1)[0], sorted_pairs(p.collide()[0]),
+               p.visible_lights(cam, R.F_LIGHT_SPOT).tolist(), p.get_indexes_for_components([L.C_POSITION, L.C_VELOCITY]).tolist(), p.export_entities(ids[:40]).tobytes()]
+        assert out[0] > 0 and len(out[1]) > 0 and len(out[2]) > 0 and len(out[3]) > 0 and len(out[4]) > 0 and len(out[6]) > 0
+        return out
+
+    def cycle(p):
+        answers = []
+        ents = worlds[0]
+        p.replace_world(ents)
+        answers.append(flows(p, ents))
+        still = int(ents["id"][-1])                                       # a border entity of query_world: no Velocity, so no slot of the dynamic table
+        assert not ents["flags"][-1] & (R.F_HAS_VEL | R.F_HAS_ROTVEL)
+        add = ents[:1].copy(); add["id"] = int(ents["id"].max()) + 1; add["pos"] += np.float32(7.5)
+        ch = np.zeros(3, R.CHANGE_DT)
+        ch[0] = (L.CHANGE_MODIFY, int(ents["id"][5]), L.C_POSITION, 0, (8200, 8190, 8210, 0))      # (the small-batch staging block)
+        ch[1] = (L.CHANGE_ADD_ENTITY, int(add["id"][0]), 0, 0, (0, 0, 0, 0))                         # row_cap == n after an upload: every column grows
+        ch[2] = (L.CHANGE_MODIFY, still, L.C_VELOCITY, 0, (3, 0, 0, 0))                             # the dynamic table grows
+        answers.append(p.apply_changes(ch, added=add))
+        t = p.tick(0.25)
+        assert t["n_changed"] > 0 and t["n_rebucket"] > 0                  # movers: the re-bucket scratch exists
+        answers.append(t)
+        p.replace_world(worlds[1])
+        answers.append(flows(p, worlds[1]))
+        p.replace_world(static_world)
+        switches = p.stats()["reserved"]
+        p.cull_and_pack(cam); p.tick(0.016)                                # the static cache freezes here
+        for i in range(12):
+            c2 = R.Camera((8192 + 9.5 * i, 8192 - 4.25 * i, 8500 - 11.0 * i), (0.02 * i, 0.01 * i, -1), 900.0)
+            p.cull_and_pack(c2, asynchronous=True, copy=False, defer_pack=True, two_lanes=True); p.tick(0.016, asynchronous=True)
+        vis, _ = p.wait(copy=True)
+        answers.append((vis["total"], vis["ids"].tobytes()))
+        assert p.stats()["reserved"] - switches >= 12                      # lane switches: the second lane really existed
+        p.replace_world(worlds[0])
+        return answers
+
+    base = live()
+    p = R.Pipeline(16384, 64, flags=L.CFG_PROBE)
+    p.set_entity_logic([(TYPE_A, L.LOGIC_ENTITY)])
+    p.set_model_lod(int(worlds[0]["model_index"][0]), int(worlds[0]["render_system"][0]), [0, 150, 300], [150, 300, 450])
+    seen, counts = [], []
+    for _ in range(3):
+        seen.append(cycle(p)); counts.append(live() - base)
+    print("live blocks after each cycle:", counts)
+    assert counts[0] > 0 and counts[0] == counts[1] == counts[2], counts
+    assert_clean_publication(p)
+    for a, b in zip(seen[0], seen[2]):
+        np.testing.assert_equal(a, b)
+    p.close()
+    assert live() == base
+    # the device re-bucket's scratch and pinned staging block (plain contexts only): allocated by a tick with movers, gone with the next upload
+    q = R.Pipeline(16384, 64)
+    counts = []
+    for _ in range(3):
+        q.replace_world(worlds[0]); q.cull_and_pack(cam)
+        counts.append(live())
+        assert q.tick(0.25)["n_rebucket"] > 0 and live() > counts[-1] + 30      # (more than 30 scratch buffers)
+    assert q.stats()["n_device_rebuckets"] == 3 and counts[1] == counts[2], counts
+    assert_clean_publication(q)
+    q.close()
+    assert live() == base
