@@ -419,6 +419,35 @@ typedef struct { uint32_t query, entity_id; float t_enter, t_exit; } re_segment_
 int re_query_segments(re_ctx *ctx, const re_segment *segments, uint32_t n, const re_box_query_args *args,
                       re_segment_hit *hits, uint32_t capacity, uint32_t *n_total);
 
+/* The third question: who is within r of this point -- an explosion, a proximity trigger, a sun's reach, a producer looking for asteroids.  For a whole
+ * batch of spheres at once: every record (query index, entity id, dist_sq, side) such that
+ *   the entity is one re_query_boxes would consider (live, in the tree, no RE_F_PHANTOM replica, no ghost instance; args filters as there, and
+ *   RE_F_STATIC follows the tree), is not the sphere's exclude_entity (RE_SPHERE_NO_ENTITY: none), and
+ *   its stored StaticAABB (RE_C_STATIC_AABB, unclipped) lies within the radius of the centre c by this test, in plain f32 -- every operation rounds once,
+ *   no contraction, compares written as compares --, with r2 = r * r (one f32 multiplication, made by the host and carried in the query record):
+ *       side = 0
+ *       for a in x, y, z:   (mn, mx = the box's bounds on a)
+ *           if      c[a] < mn:  e[a] = mn - c[a];  side |= 1 << a
+ *           else if c[a] > mx:  e[a] = c[a] - mx;  side |= 16 << a
+ *           else:               e[a] = 0
+ *       dist_sq = (e[x]*e[x] + e[y]*e[y]) + e[z]*e[z]
+ *       hit iff dist_sq <= r2
+ *   The test is closed: a sphere that only touches a face, an edge or a corner hits.  r == 0 is a point query.  side == 0 exactly when the centre is
+ *   inside the box, and then dist_sq == 0.  An overflowing product gives inf, which misses.
+ * Each pair is reported once, in no particular order; the nearest entity of a query is the record with the smallest (dist_sq, entity_id), found by the caller.
+ * *n_total, capacity, hits and the calling contract are those of re_query_boxes: synchronous, valid at any point between calls, an asynchronous cull or
+ * tick in flight is finished first, no frame stamps read; *n_total is exact even with capacity == 0, the first `capacity` records are written.
+ * RE_E_ARG (the message names the first offending sphere, the whole batch is checked before anything is touched): a non-finite centre or radius,
+ * radius < 0, |centre[a]| or radius above 64 * outline_length (the rounding of c +- r and of the test stays below the margin of the walk), nonzero
+ * reserved, a sphere whose bounding cube exceeds RE_BOX_QUERY_MAX_CELLS candidate world sections (a radius of 14 atomic lengths passes),
+ * n > RE_BOX_QUERY_MAX_QUERIES, nonzero reserved words of args, capacity without a buffer.  RE_E_STATE before any upload.  n == 0, or a world without
+ * entities: no hits. */
+typedef struct { float centre[3], radius; uint32_t exclude_entity /* RE_SPHERE_NO_ENTITY: none */, reserved /* 0 */; } re_sphere;   /* 24 bytes */
+typedef struct { uint32_t query, entity_id; float dist_sq; uint32_t side; } re_sphere_hit;                                          /* 16 bytes */
+#define RE_SPHERE_NO_ENTITY 0xFFFFFFFFu
+int re_query_spheres(re_ctx *ctx, const re_sphere *spheres, uint32_t n, const re_box_query_args *args,
+                     re_sphere_hit *hits, uint32_t capacity, uint32_t *n_total);
+
 /* ECS read-back for user logic (LogicFunction reads components through &ECS, exports/logic_components.rs:15-18).  A component the entity does not
  * carry (never written, or removed by RE_CHANGE_REMOVE_COMPONENT) yields RE_E_ARG == ECS::get_copy -> None (objects/ecs.rs:653-664). */
 int re_read_component(re_ctx *ctx, uint32_t entity_id, int component, void *dst);

@@ -426,6 +426,32 @@ class Pipeline {
         }
         return first;
     }
+    // ... and who is within r of a point -- an explosion, a proximity trigger, a producer looking for asteroids: the entities whose StaticAABB lies within the
+    // radius of each centre, as (index of the sphere, entity, dist_sq, side) records in no particular order, each pair once; dist_sq is the squared distance
+    // from the centre to the box (0 with side == 0 for a centre inside it), the test is closed.  exclude_entity of a sphere is not reported
+    // (RE_SPHERE_NO_ENTITY: none).  nearest_hits picks the nearest of each sphere.
+    struct Sphere { TVec3 centre; float radius = 0.0f; EntityId exclude_entity = RE_SPHERE_NO_ENTITY; };
+    std::vector<re_sphere_hit> find_entities_within_radius(const std::vector<Sphere> &spheres, uint32_t need_flags = 0u, uint32_t forbid_flags = 0u) {
+        upload_if_needed();
+        std::vector<re_sphere> s; s.reserve(spheres.size());
+        for (const Sphere &g : spheres) s.push_back(re_sphere{ { g.centre.x, g.centre.y, g.centre.z }, g.radius, g.exclude_entity, 0u });
+        const re_box_query_args args{ need_flags, forbid_flags, { 0u, 0u } };
+        uint32_t n = 0; check(re_query_spheres(ctx_, s.data(), (uint32_t)s.size(), &args, nullptr, 0u, &n), "re_query_spheres");
+        std::vector<re_sphere_hit> hits(n);
+        if (n) check(re_query_spheres(ctx_, s.data(), (uint32_t)s.size(), &args, hits.data(), n, &n), "re_query_spheres");
+        hits.resize(std::min<size_t>(hits.size(), n));
+        return hits;
+    }
+    // per sphere 0 .. n - 1 the record with the smallest (dist_sq, entity_id), or nothing: the nearest entity.  The ordering is the host's.
+    static std::vector<std::optional<re_sphere_hit>> nearest_hits(const std::vector<re_sphere_hit> &hits, size_t n) {
+        std::vector<std::optional<re_sphere_hit>> nearest(n);
+        for (const re_sphere_hit &h : hits) {
+            if (h.query >= n) continue;
+            std::optional<re_sphere_hit> &f = nearest[h.query];
+            if (!f || h.dist_sq < f->dist_sq || (h.dist_sq == f->dist_sq && h.entity_id < f->entity_id)) f = h;
+        }
+        return nearest;
+    }
     bool has_component(EntityId e, uint32_t ecs_bit) { upload_if_needed(); uint32_t bits = 0; check(re_ecs_bitset(ctx_, e, &bits), "re_ecs_bitset"); return (bits >> ecs_bit) & 1u; }   // ecs_bit: RE_ECS_BIT_*
     re_ctx *context() { upload_if_needed(); return ctx_; }
 

@@ -29,6 +29,9 @@ pub const RE_BOX_QUERY_MAX_CELLS: u32 = 32768; pub const RE_BOX_QUERY_MAX_QUERIE
 #[repr(C)] #[derive(Copy, Clone)] pub struct ReSegment { pub p0: [f32; 3], pub p1: [f32; 3], pub exclude_entity: u32, pub reserved: u32 }          // 32 bytes; exclude_entity: RE_SEGMENT_NO_ENTITY for none; reserved must be 0
 #[repr(C)] #[derive(Copy, Clone)] pub struct ReSegmentHit { pub query: u32, pub entity_id: u32, pub t_enter: f32, pub t_exit: f32 }             // 16 bytes
 pub const RE_SEGMENT_NO_ENTITY: u32 = 0xFFFF_FFFF;
+#[repr(C)] #[derive(Copy, Clone)] pub struct ReSphere { pub centre: [f32; 3], pub radius: f32, pub exclude_entity: u32, pub reserved: u32 }            // 24 bytes; exclude_entity: RE_SPHERE_NO_ENTITY for none; reserved must be 0
+#[repr(C)] #[derive(Copy, Clone)] pub struct ReSphereHit { pub query: u32, pub entity_id: u32, pub dist_sq: f32, pub side: u32 }                 // 16 bytes; side bit a: beyond the minimum face of axis a, bit 4 + a: beyond the maximum face; 0: the centre is inside
+pub const RE_SPHERE_NO_ENTITY: u32 = 0xFFFF_FFFF;
 #[repr(C)] pub struct ReGathered { pub n_ranks: u32, pub overflowed: u32, pub counts: *const u32, pub d_entity_ids: *const u32, pub ids_rank_stride: u32,
                                    pub d_matrices: *const f32, pub matrices_rank_stride: u32 }
 #[repr(C)] #[derive(Copy, Clone, Default)] pub struct ReEntityState { pub entity_id: u32, pub model_index: u32, pub render_system: u32, pub sortable: u32, pub flags: u32,
@@ -74,6 +77,7 @@ extern "C" {
     pub fn re_logic_list(ctx: *mut ReCtx, flags: u32, calls: *mut ReLogicCall, capacity: u32, n_total: *mut u32) -> c_int;
     pub fn re_query_boxes(ctx: *mut ReCtx, boxes6: *const f32 /* [n * 6]: xmin xmax ymin ymax zmin zmax */, n: u32, args: *const ReBoxQueryArgs, hits: *mut ReBoxHit, capacity: u32, n_total: *mut u32) -> c_int;
     pub fn re_query_segments(ctx: *mut ReCtx, segments: *const ReSegment, n: u32, args: *const ReBoxQueryArgs, hits: *mut ReSegmentHit, capacity: u32, n_total: *mut u32) -> c_int;
+    pub fn re_query_spheres(ctx: *mut ReCtx, spheres: *const ReSphere, n: u32, args: *const ReBoxQueryArgs, hits: *mut ReSphereHit, capacity: u32, n_total: *mut u32) -> c_int;
     pub fn re_wait(ctx: *mut ReCtx, vis: *mut ReVisible, tick: *mut ReTickResult) -> c_int;
     pub fn re_copy_visible(ctx: *mut ReCtx, ids: *mut u32, mats: *mut f32, capacity: u32, n_written: *mut u32) -> c_int;
     pub fn re_set_output_buffers(ctx: *mut ReCtx, d_ids: *mut u32, d_mats: *mut f32, capacity: u32) -> c_int;

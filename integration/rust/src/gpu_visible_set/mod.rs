@@ -10,7 +10,7 @@ use std::ffi::CStr;
 use std::mem::MaybeUninit;
 
 /// One resident copy of the world on one GPU.
-pub struct GpuVisibleSet { ctx: *mut ReCtx, collision_pairs: Vec<ReCollision>, logic_list: Vec<ReLogicCall>, box_hits: Vec<ReBoxHit>, segment_hits: Vec<ReSegmentHit> }
+pub struct GpuVisibleSet { ctx: *mut ReCtx, collision_pairs: Vec<ReCollision>, logic_list: Vec<ReLogicCall>, box_hits: Vec<ReBoxHit>, segment_hits: Vec<ReSegmentHit>, sphere_hits: Vec<ReSphereHit> }
 
 // the context is driven from the render thread only (Pipeline::execute), like the flows it replaces
 unsafe impl Send for GpuVisibleSet {}
@@ -51,7 +51,7 @@ impl GpuVisibleSet {
         let mut ctx: *mut ReCtx = std::ptr::null_mut();
         let rc = unsafe { re_create(&cfg, &mut ctx) };
         if rc != RE_OK { return Err(GpuError { code: rc, message: last_error(std::ptr::null()) }); }
-        Ok(GpuVisibleSet { ctx, collision_pairs: Vec::with_capacity(4096), logic_list: Vec::with_capacity(4096), box_hits: Vec::with_capacity(4096), segment_hits: Vec::with_capacity(4096) })
+        Ok(GpuVisibleSet { ctx, collision_pairs: Vec::with_capacity(4096), logic_list: Vec::with_capacity(4096), box_hits: Vec::with_capacity(4096), segment_hits: Vec::with_capacity(4096), sphere_hits: Vec::with_capacity(4096) })
     }
 
     fn check(&self, rc: i32) -> Result<(), GpuError> {
@@ -343,6 +343,34 @@ impl GpuVisibleSet {
             if nearer { *slot = Some(*h); }
         }
         first
+    }
+
+    /// Who is within r of a point -- an explosion, a proximity trigger, a producer looking for asteroids: the entities whose StaticAABB lies within the
+    /// radius of each centre of a batch, as (query index, entity id, dist_sq, side) records in no particular order, each pair once; dist_sq is the squared
+    /// distance from the centre to the box (0 with side == 0 for a centre inside it), the test is closed.  `exclude_entity` is not reported
+    /// (`RE_SPHERE_NO_ENTITY`: nobody); `filter` as `entities_in_boxes`.  Valid at any point between calls.
+    pub fn entities_within_radius(&mut self, spheres: &[ReSphere], filter: Option<&ReBoxQueryArgs>) -> Result<&[ReSphereHit], GpuError> {
+        let args = filter.map_or(std::ptr::null(), |f| f as *const ReBoxQueryArgs);
+        loop {
+            let mut n = 0u32;
+            let cap = self.sphere_hits.capacity() as u32;
+            let rc = unsafe { ffi::re_query_spheres(self.ctx, spheres.as_ptr(), spheres.len() as u32, args, self.sphere_hits.as_mut_ptr(), cap, &mut n) };
+            self.check(rc)?;
+            if n <= cap { unsafe { self.sphere_hits.set_len(n as usize) }; return Ok(&self.sphere_hits); }
+            self.sphere_hits = Vec::with_capacity(n as usize + n as usize / 4);         // more records than the buffer holds: once more with room
+        }
+    }
+
+    /// The nearest entity of each of `n` spheres: per query index the record with the smallest (dist_sq, entity_id), or None.  The ordering is the
+    /// host's; the device reports every hit.
+    pub fn nearest_hits(hits: &[ReSphereHit], n: usize) -> Vec<Option<ReSphereHit>> {
+        let mut nearest: Vec<Option<ReSphereHit>> = vec![None; n];
+        for h in hits {
+            let Some(slot) = nearest.get_mut(h.query as usize) else { continue };
+            let nearer = match slot { None => true, Some(f) => h.dist_sq < f.dist_sq || (h.dist_sq == f.dist_sq && h.entity_id < f.entity_id) };
+            if nearer { *slot = Some(*h); }
+        }
+        nearest
     }
 
     /// flows/logic_flow.rs:230 + the kinematic part of :255 (update_positions, apply_change of the kinematic requests).

@@ -75,7 +75,7 @@ struct ListChannel {
     uint32_t next_seq() { return ++calls; }
     int wait(re_ctx *c, uint32_t seq, uint32_t *n);       // completion of call `seq`: polls the sequence number the last workgroup publishes (a stream synchronise costs tens of microseconds)
 };
-// One kind of tree query (re_query_boxes, re_query_segments): the batch travels from two pinned buffers that alternate by call into one device array; records
+// One kind of tree query (re_query_boxes, re_query_segments, re_query_spheres): the batch travels from two pinned buffers that alternate by call into one device array; records
 // come back through d_out; header block, mapped block and sequence numbers of its own.  Allocated lazily, kept across uploads.
 template <class Query> struct QueryFlow {
     Pinned h_q[2]; uint32_t k = 0; DevBuf<Query> d_q; DevBuf<unsigned long long> d_out; ListChannel ch;
@@ -305,7 +305,7 @@ struct re_ctx : DeviceBytes, WorldState {
     // entity logic (re_logic_list): the logic table and the channel belong to the flow and survive uploads (the row lists are the world's: WorldState)
     std::vector<re_entity_logic> logic_table; std::unordered_map<uint64_t, uint32_t> logic_index;   // TypeIdentifier -> table index
     ListChannel logic;
-    QueryFlow<BoxQuery> boxq; QueryFlow<SegQuery> segq;                        // tree queries (re_query_boxes, re_query_segments)
+    QueryFlow<BoxQuery> boxq; QueryFlow<SegQuery> segq; QueryFlow<SphQuery> sphq;      // tree queries (re_query_boxes, re_query_segments, re_query_spheres)
 };
 
 #define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return (ctx)->fail(RE_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
@@ -4050,7 +4050,7 @@ extern "C" int re_logic_list(re_ctx *c, uint32_t flags, re_logic_call *calls, ui
 
 // ------------------------------------------------------------------------------------------------
 // Tree queries for user logic: what a LogicFunction / CollisionFunction / UserInputLogicFunction reads out of its &BoundingBoxTree
-// (exports/logic_components.rs:14-18) -- the entities in a batch of boxes and along a batch of segments (k_box_query, k_segment_query: re_treequery.hip).  The tree lives on the device only.
+// (exports/logic_components.rs:14-18) -- the entities in a batch of boxes, along a batch of segments and within a radius of a batch of points (k_box_query, k_segment_query, k_sphere_query: re_treequery.hip).  The tree lives on the device only.
 // ------------------------------------------------------------------------------------------------
 static_assert(sizeof(re_box_hit) == 8 && sizeof(re_box_query_args) == 16 && sizeof(BoxQuery) == 64, "record layouts of include/re_hip.h / re_kernels.h");
 // one box as the kernel gets it; the candidate cells of all levels, counted with the kernel's own arithmetic (box_level_range)
@@ -4069,7 +4069,7 @@ static uint64_t make_box_query(const float *b, uint32_t outline, uint32_t atomic
     q->ncells = (uint32_t)std::min<uint64_t>(cells, 0xFFFFFFFFull);
     return cells;
 }
-// What the two calls share, from the argument checks to *n_total.  `call`, `plural`, `argument`: the names in the messages; build(i, &q) checks query i and
+// What the three calls share, from the argument checks to *n_total.  `call`, `plural`, `argument`: the names in the messages; build(i, &q) checks query i and
 // writes its record, or fails naming it; rec_words: 8-byte words of an output record; A: the kernel's argument block with the kernel's own members set.
 template <class Query, class KArgs, class Build>
 static int run_tree_query(re_ctx *c, const char *call, const char *plural, const char *argument, QueryFlow<Query> &F, const void *queries, uint32_t n, const re_box_query_args *args,
@@ -4160,3 +4160,38 @@ extern "C" int re_query_segments(re_ctx *c, const re_segment *segments, uint32_t
     };
     return run_tree_query(c, "re_query_segments", "segments", "segments", c->segq, segments, n, args, hits, capacity, n_total, build, 2u, k_segment_query, A);
 } RE_ABI_GUARD(c, "re_query_segments")
+
+// ... and the entities within a radius of each point of a batch (k_sphere_query): the same contract, a channel of its own
+static_assert(sizeof(re_sphere) == 24 && sizeof(re_sphere_hit) == 16 && sizeof(SphQuery) == 64, "record layouts of include/re_hip.h / re_kernels.h");
+extern "C" int re_query_spheres(re_ctx *c, const re_sphere *spheres, uint32_t n, const re_box_query_args *args, re_sphere_hit *hits, uint32_t capacity, uint32_t *n_total) try {
+    if (!c) return RE_E_ARG;
+    SphQueryArgs A{};
+    A.outline = c->cfg.outline_length; A.margin = segment_query_margin(c->cfg.outline_length);
+    const float margin = A.margin, limit = 64.0f * (float)c->cfg.outline_length;
+    auto build = [&](uint32_t i, SphQuery *out) {
+        const re_sphere &s = spheres[i];
+        if (s.reserved) return c->fail(RE_E_ARG, "re_query_spheres: sphere %u: reserved must be 0", i);
+        if (!std::isfinite(s.radius) || !std::isfinite(s.centre[0]) || !std::isfinite(s.centre[1]) || !std::isfinite(s.centre[2]))
+            return c->fail(RE_E_ARG, "re_query_spheres: sphere %u is not finite (its centre or its radius)", i);
+        if (s.radius < 0.0f) return c->fail(RE_E_ARG, "re_query_spheres: sphere %u has a negative radius", i);
+        // magnitudes of at most outline * 2^7 (with c +- r) keep one ulp at outline * 2^-16, below the margin of outline * 2^-12
+        if (s.radius > limit || std::fabs(s.centre[0]) > limit || std::fabs(s.centre[1]) > limit || std::fabs(s.centre[2]) > limit)
+            return c->fail(RE_E_ARG, "re_query_spheres: sphere %u lies beyond 64 outline lengths (a centre coordinate or the radius)", i);
+        SphQuery &q = *out;
+        float bb[6];
+        for (int a = 0; a < 3; a++) {
+            q.c[a] = s.centre[a];
+            const float lo = s.centre[a] - s.radius, hi = s.centre[a] + s.radius;
+            bb[2 * a] = lo - margin; bb[2 * a + 1] = hi + margin;
+        }
+        q.r2 = s.radius * s.radius;
+        // the candidate cells are those of the bounding cube, inflated by the margin: the rounding of c +- r and of the test stays below it
+        BoxQuery b;
+        const uint64_t cells = make_box_query(bb, c->cfg.outline_length, c->cfg.atomic_length, c->maxlevel, &b);
+        if (cells > RE_BOX_QUERY_MAX_CELLS) return c->fail(RE_E_ARG, "re_query_spheres: the bounding cube of sphere %u covers %llu candidate cells (at most %u: a radius of 14 atomic lengths passes)", i, (unsigned long long)cells, RE_BOX_QUERY_MAX_CELLS);
+        q.exclude = s.exclude_entity; q.flags = b.flags; q.ncells = b.ncells; q.pad[0] = q.pad[1] = q.pad[2] = 0;
+        for (int a = 0; a < 3; a++) { q.umin[a] = b.umin[a]; q.umax[a] = b.umax[a]; }
+        return (int)RE_OK;
+    };
+    return run_tree_query(c, "re_query_spheres", "spheres", "spheres", c->sphq, spheres, n, args, hits, capacity, n_total, build, 2u, k_sphere_query, A);
+} RE_ABI_GUARD(c, "re_query_spheres")

@@ -451,7 +451,11 @@ struct SegQuery { float p0[3], d[3]; uint32_t exclude, umin[3], umax[3], flags, 
 // The margin by which the prune inflates a cell's box (and the host the bounding box): outline * 2^-12.  The slab test's rounding error in world units is
 // bounded by about outline * 2^-21 -- three rounded operations on t <= 1 times |d| <= sqrt(3) * outline, plus the ulp of the coordinates.
 RE_HD float segment_query_margin(uint32_t outline) { return (float)outline * (1.0f / 4096.0f); }
-// The argument blocks of the two kernels: one head and one tail, and between them what a kernel has of its own -- the query records, and the segment's
+// ... and the entities within a radius of each point of a batch
+// One sphere as the host builds it (re_query_spheres): the centre, r2 = r * r (one f32 multiplication), the excluded entity, and the bounding cube
+// [(c - r) - m, (c + r) + m] per axis, m = segment_query_margin(outline), as make_box_query leaves it: the candidate cells are that box's.
+struct SphQuery { float c[3], r2; uint32_t exclude, umin[3], umax[3], flags, ncells, pad[3]; };      // 64 bytes
+// The argument blocks of the three kernels: one head and one tail, and between them what a kernel has of its own -- the query records, and the segment's
 // prune parameters.  (The head's eight words lead: the build preloads the first kernel-argument dwords into SGPRs.)
 struct TreeQueryHead {
     uint32_t n, n_sh_chunks;                // queries; 256-entry chunks of the shared table (the grid: n workgroups, then n_sh_chunks per tile of BOXQ_TILE queries)
@@ -467,10 +471,14 @@ struct BoxQueryOwn { const BoxQuery *q; };
 struct SegQueryOwn { uint32_t outline; float margin; const SegQuery *q; };
 struct BoxQueryArgs : TreeQueryHead, BoxQueryOwn, TreeQueryWorld {};
 struct SegQueryArgs : TreeQueryHead, SegQueryOwn, TreeQueryWorld {};
-static_assert(sizeof(BoxQueryArgs) == sizeof(TreeQueryHead) + sizeof(BoxQueryOwn) + sizeof(TreeQueryWorld) && sizeof(SegQueryArgs) == sizeof(TreeQueryHead) + sizeof(SegQueryOwn) + sizeof(TreeQueryWorld),
+struct SphQueryOwn { uint32_t outline; float margin; const SphQuery *q; };
+struct SphQueryArgs : TreeQueryHead, SphQueryOwn, TreeQueryWorld {};
+static_assert(sizeof(BoxQueryArgs) == sizeof(TreeQueryHead) + sizeof(BoxQueryOwn) + sizeof(TreeQueryWorld) && sizeof(SegQueryArgs) == sizeof(TreeQueryHead) + sizeof(SegQueryOwn) + sizeof(TreeQueryWorld) &&
+              sizeof(SphQueryArgs) == sizeof(TreeQueryHead) + sizeof(SphQueryOwn) + sizeof(TreeQueryWorld),
               "the parts lie one behind the other, without padding");
 __global__ void k_box_query(BoxQueryArgs A);
 __global__ void k_segment_query(SegQueryArgs A);
+__global__ void k_sphere_query(SphQueryArgs A);
 hipError_t sort_pairs_u64_u32(void *tmp, size_t *tmp_bytes, const uint64_t *keys_in, uint64_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out,
                               uint32_t n, unsigned begin_bit, unsigned end_bit, hipStream_t stream);      // re_sort.hip (rocPRIM radix sort)
 __global__ void k_rb_ovl_insert(uint32_t n, const Pair64 *pairs, RbTables T);

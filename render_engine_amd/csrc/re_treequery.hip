@@ -1,7 +1,8 @@
 // Tree queries for user logic on the resident world, for gfx950 -- what a LogicFunction / CollisionFunction / UserInputLogicFunction of the reference
 // (exports/logic_components.rs:14-18) reads out of its &BoundingBoxTree (find_all_unique_world_section_ids, stored_entities_indexes,
-// shared_section_indexes): "who is near this box" (k_box_query) and "who lies along this segment" -- a shot, a line of sight, a pick ray (k_segment_query).
-// One walk of the tree, written once over a query shape; the two kernels instantiate it.
+// shared_section_indexes): "who is near this box" (k_box_query), "who lies along this segment" -- a shot, a line of sight, a pick ray (k_segment_query) --
+// and "who is within r of this point" -- an explosion, a proximity trigger (k_sphere_query).
+// One walk of the tree, written once over a query shape; the three kernels instantiate it.
 //
 // The rule of the boxes: (query i, entity) for every live entity in the tree (not F_DEAD, not an F_PHANTOM replica, row_cell set; ghost instances of the
 // frozen static cache are no entities) whose stored StaticAABB intersects box i by StaticAABB::intersect (aabb.rs:68-73: closed intervals, plain f32
@@ -9,13 +10,18 @@
 // The rule of the segments: (query i, entity, t_enter, t_exit) for every entity the box query would consider other than the segment's excluded one whose
 // stored, unclipped StaticAABB is met by the segment p0 + t * d, t in [0, 1], by the slab test below: plain f32, IEEE division, closed intervals, d == 0 on
 // an axis a containment test.  Each pair once; tests/segment_rule.py restates it.
+// The rule of the spheres: (query i, entity, dist_sq, side) for every entity the box query would consider other than the sphere's excluded one whose
+// stored, unclipped StaticAABB lies within the radius of the centre by sphq_dist_sq below: plain f32, every operation rounded once, compares written as
+// compares, dist_sq <= r2 with r2 = r * r multiplied once on the host.  Each pair once; tests/sphere_rule.py restates it.
 //
 // The walk: an entity's sections are a function of its AABB clipped to the world (normalize_aabb); clipping is monotone per axis, so two
 // intersecting intervals still intersect after it, and every entity of the rule has a section key inside the query's cell range of that key's level
 // (box_level_range, re_kernels.h; tests/test_box_query_rule.py shows it against the oracle).  The exact test then runs on the stored boxes.  A segment
 // walks the cell ranges of its bounding box (inflated by the margin), with one test more in front of every probe: a candidate
 // cell is looked up only when the segment meets the cell's own box -- inflated by the margin, and open-ended on an axis where the cell lies on a face of
-// the world, because entities clipped to the world sit there and the exact test runs on unclipped boxes.
+// the world, because entities clipped to the world sit there and the exact test runs on unclipped boxes.  A sphere walks the cell ranges of its bounding
+// cube (inflated likewise) and prunes a cell whose box -- the segments' cell box -- lies further from the centre than the radius, by the exact test's own
+// function: f32 subtract, multiply and add are monotone, so the distance to a box that contains an entity's clipped AABB never exceeds the entity's.
 //   unique sections: one workgroup per query enumerates the candidate cells of every level, prunes (segments), looks the remaining keys up (rb_find) and
 //     walks the rows of the sections that exist, one wave per section, one lane per row;
 //   shared sections: their links to the unique sections are not on the device, so they are taken from their own side: workgroups behind the first n
@@ -134,6 +140,69 @@ struct SegShape {
         unsigned long long *o = A.out + (size_t)slot * 2u;
         __hip_atomic_store(o, (unsigned long long)r.query | ((unsigned long long)r.id << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(o + 1, (unsigned long long)__float_as_uint(r.t0) | ((unsigned long long)__float_as_uint(r.t1) << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
+
+// ---- spheres ----------------------------------------------------------------------------------------------------------------------------------------
+// one axis of the distance from a point to a closed interval (bounds may be infinite: both compares are false then and e = 0); the side bit a the minimum
+// face, 16 << a the maximum face
+__device__ __forceinline__ float sphq_axis(float c, float mn, float mx, uint32_t lo_bit, uint32_t hi_bit, uint32_t &side) {
+    if (c < mn) { side |= lo_bit; return mn - c; }
+    if (c > mx) { side |= hi_bit; return c - mx; }
+    return 0.0f;
+}
+// the squared distance from the point c to a closed box, (ex * ex + ey * ey) + ez * ez, every operation rounded once (the library is built without
+// contraction); side == 0 exactly when the point is inside
+__device__ __forceinline__ float sphq_dist_sq(const float *c, float x0, float x1, float y0, float y1, float z0, float z1, uint32_t &side) {
+    side = 0u;
+    const float ex = sphq_axis(c[0], x0, x1, 1u, 16u, side), ey = sphq_axis(c[1], y0, y1, 2u, 32u, side), ez = sphq_axis(c[2], z0, z1, 4u, 64u, side);
+    return (ex * ex + ey * ey) + ez * ez;
+}
+
+struct SphRec { uint32_t query, id; float dist_sq; uint32_t side; };      // re_sphere_hit
+
+struct SphShape {
+    using Args = SphQueryArgs; using Query = SphQuery; using Rec = SphRec;
+    using CellBox = SegShape::CellBox;
+    static constexpr uint32_t TILE_WORDS = 12;     // a sphere in the LDS tile of the shared part: umin[3], umax[3], flags, c[3], r2, exclude
+    float c[3], r2; uint32_t exclude;
+    static __device__ __forceinline__ void stage(SphShape &L, const Query &Q, uint32_t tid) {
+        if (tid < 3u) L.c[tid] = Q.c[tid];
+        if (tid == 3u) { L.r2 = Q.r2; L.exclude = Q.exclude; }
+    }
+    static __device__ __forceinline__ void to_tile(const Query &Q, uint32_t *t) {
+        for (uint32_t a = 0; a < 3u; a++) t[a] = __float_as_uint(Q.c[a]);
+        t[3] = __float_as_uint(Q.r2); t[4] = Q.exclude;
+    }
+    static __device__ __forceinline__ SphShape from_tile(const uint32_t *t) {
+        SphShape P;
+#pragma unroll
+        for (int a = 0; a < 3; a++) P.c[a] = __uint_as_float(t[a]);
+        P.r2 = __uint_as_float(t[3]); P.exclude = t[4];
+        return P;
+    }
+    static __device__ __forceinline__ CellBox cell_box(const Args &A, const uint32_t *c0, const uint32_t *c1) {      // the segments' cell box
+        return { segq_cell_min(c0[0], A.margin), segq_cell_max(c1[0], A.outline, A.margin), segq_cell_min(c0[1], A.margin), segq_cell_max(c1[1], A.outline, A.margin),
+                 segq_cell_min(c0[2], A.margin), segq_cell_max(c1[2], A.outline, A.margin) };
+    }
+    // the prune, by the exact test's own function: the cell's box holds the clipped AABB of every entity there and is open-ended where they were clipped,
+    // and f32 subtract, multiply and add are monotone, so dist_sq(cell) <= dist_sq(entity)
+    __device__ __forceinline__ bool misses(const CellBox &b) const {
+        uint32_t side;
+        return sphq_dist_sq(c, b.x0, b.x1, b.y0, b.y1, b.z0, b.z1, side) > r2;
+    }
+    __device__ __forceinline__ bool test(const Aabb &a, const uint32_t *id, uint32_t query, Rec &rec) const {
+        rec.query = query; rec.id = *id;
+        if (rec.id == exclude) return false;
+        rec.dist_sq = sphq_dist_sq(c, a.xmin, a.xmax, a.ymin, a.ymax, a.zmin, a.zmax, rec.side);
+        return rec.dist_sq <= r2;
+    }
+    // write-through stores, as the segment query's; two 8-byte halves, both below the capacity or neither
+    static __device__ __forceinline__ void store(const Args &A, uint32_t slot, const Rec &r) {
+        if (slot >= A.capacity) return;
+        unsigned long long *o = A.out + (size_t)slot * 2u;
+        __hip_atomic_store(o, (unsigned long long)r.query | ((unsigned long long)r.id << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(o + 1, (unsigned long long)__float_as_uint(r.dist_sq) | ((unsigned long long)r.side << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 };
 
@@ -338,5 +407,6 @@ template <class Shape> __device__ __forceinline__ void treeq_kernel(const typena
 
 __global__ __launch_bounds__(BOXQ_THREADS) void k_box_query(BoxQueryArgs A) { __shared__ TreeqShared<BoxShape> S; treeq_kernel(A, S); }
 __global__ __launch_bounds__(BOXQ_THREADS) void k_segment_query(SegQueryArgs A) { __shared__ TreeqShared<SegShape> S; treeq_kernel(A, S); }
+__global__ __launch_bounds__(BOXQ_THREADS) void k_sphere_query(SphQueryArgs A) { __shared__ TreeqShared<SphShape> S; treeq_kernel(A, S); }
 
 }  // namespace re

@@ -197,6 +197,22 @@ def first_hits(hits, n):
     return first, found
 
 
+def nearest_hits(hits, n):
+    """the nearest entity of each of the n spheres of a Pipeline.find_entities_within_radius answer: (nearest, found) with nearest a SPHERE_HIT_DT array of
+    n records -- the record with the smallest (dist_sq, entity_id) of query i at index i -- and found[i] False where sphere i hit nothing (nearest[i] is
+    then zero but for its query index).  The ordering is the host's: the device reports every hit."""
+    nearest = np.zeros(n, _capi.SPHERE_HIT_DT)
+    nearest["query"] = np.arange(n, dtype=np.uint32)
+    found = np.zeros(n, bool)
+    if len(hits):
+        order = np.lexsort((hits["entity_id"], hits["dist_sq"], hits["query"]))
+        q = hits["query"][order]
+        lead = order[np.concatenate([[True], q[1:] != q[:-1]])]
+        nearest[hits["query"][lead]] = hits[lead]
+        found[hits["query"][lead]] = True
+    return nearest, found
+
+
 class Pipeline:
     """One GPU's share of the world: BoundingBoxTree + ECS columns resident in HBM."""
 
@@ -421,6 +437,22 @@ class Pipeline:
             seg["exclude_entity"] = _capi.SEGMENT_NO_ENTITY if exclude is None else np.asarray(exclude, np.uint32)
         args = _capi.BoxQueryArgs(int(need_flags), int(forbid_flags)) if (need_flags or forbid_flags) else None
         return self._record_list(self._L.re_query_segments, (seg.ctypes.data, len(seg), args), "re_query_segments", capacity, _capi.SEGMENT_HIT_DT)
+
+    def find_entities_within_radius(self, spheres, exclude=None, need_flags=0, forbid_flags=0, capacity=None):
+        """the entities whose StaticAABB lies within the radius of each point of a batch ([n, 4]: centre xyz, radius, or a SPHERE_DT array): (hits, n_total)
+        with hits a SPHERE_HIT_DT array (query, entity_id, dist_sq, side; dist_sq the squared distance from the centre to the box, 0 with side == 0 for a
+        centre inside it; side bit a: beyond the minimum face of axis a, bit 4 + a: beyond the maximum face) in no particular order; exclude: one entity id
+        per sphere that is not reported (SPHERE_NO_ENTITY: none); the filter as find_entities_in_boxes.  nearest_hits(hits, n) picks the nearest of each
+        sphere.  Valid at any point between calls."""
+        if isinstance(spheres, np.ndarray) and spheres.dtype == _capi.SPHERE_DT:
+            sph = np.ascontiguousarray(spheres)
+        else:
+            pts = np.ascontiguousarray(spheres, np.float32).reshape(-1, 4)
+            sph = np.zeros(len(pts), _capi.SPHERE_DT)
+            sph["centre"], sph["radius"] = pts[:, 0:3], pts[:, 3]
+            sph["exclude_entity"] = _capi.SPHERE_NO_ENTITY if exclude is None else np.asarray(exclude, np.uint32)
+        args = _capi.BoxQueryArgs(int(need_flags), int(forbid_flags)) if (need_flags or forbid_flags) else None
+        return self._record_list(self._L.re_query_spheres, (sph.ctypes.data, len(sph), args), "re_query_spheres", capacity, _capi.SPHERE_HIT_DT)
 
     # -- multi-GPU exchange (RCCL behind the C ABI) ---------------------------------------------------
     @staticmethod
