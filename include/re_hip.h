@@ -448,6 +448,20 @@ typedef struct { uint32_t query, entity_id; float dist_sq; uint32_t side; } re_s
 int re_query_spheres(re_ctx *ctx, const re_sphere *spheres, uint32_t n, const re_box_query_args *args,
                      re_sphere_hit *hits, uint32_t capacity, uint32_t *n_total);
 
+/* The narrower questions, answered on the device: what does this shot hit first, and who is nearest to this point.  Record i of the output is the record
+ * of query i that re_query_segments / re_query_spheres would report for the same batch and args with the smallest (t_enter, entity_id) /
+ * (dist_sq, entity_id) -- the same record bit for bit in all four fields, the one the caller used to pick out of the full list.  A query without a hit
+ * gets query = i, entity_id = RE_SEGMENT_NO_ENTITY / RE_SPHERE_NO_ENTITY and the two value words zero.  *n_found (optional): the queries with a hit.
+ * There is no capacity: the output is always n records, in query order; first / nearest == NULL with n > 0 is RE_E_ARG.  Everything else -- the rule of
+ * a hit, args, exclude_entity, the validation of every query (the message names this call), RE_E_STATE before any upload, n == 0, the calling
+ * contract (synchronous, valid at any point between calls, no frame stamps read) -- is the sibling's.  The device reduces a 64-bit key per query
+ * (the value's bits above the entity id: both values are non-negative and never NaN, so the unsigned order is the order above) and then lists the
+ * winners: 16 bytes a query come back, however many entities were hit. */
+int re_query_segments_first (re_ctx *ctx, const re_segment *segments, uint32_t n, const re_box_query_args *args,
+                             re_segment_hit *first /* [n] */, uint32_t *n_found /* optional */);
+int re_query_spheres_nearest(re_ctx *ctx, const re_sphere  *spheres,  uint32_t n, const re_box_query_args *args,
+                             re_sphere_hit  *nearest /* [n] */, uint32_t *n_found /* optional */);
+
 /* ECS read-back for user logic (LogicFunction reads components through &ECS, exports/logic_components.rs:15-18).  A component the entity does not
  * carry (never written, or removed by RE_CHANGE_REMOVE_COMPONENT) yields RE_E_ARG == ECS::get_copy -> None (objects/ecs.rs:653-664). */
 int re_read_component(re_ctx *ctx, uint32_t entity_id, int component, void *dst);

@@ -452,6 +452,31 @@ class Pipeline {
         }
         return nearest;
     }
+    // ... and the two narrower questions answered on the device (re_query_segments_first, re_query_spheres_nearest): what each segment hits first and who is
+    // nearest to each point within its radius -- element i is what first_hits / nearest_hits pick for query i out of the full answer, bit for bit, or nothing.
+    // 16 bytes a query come back instead of every hit.
+    std::vector<std::optional<re_segment_hit>> find_first_along_segments(const std::vector<Segment> &segments, uint32_t need_flags = 0u, uint32_t forbid_flags = 0u) {
+        upload_if_needed();
+        std::vector<re_segment> s; s.reserve(segments.size());
+        for (const Segment &g : segments) s.push_back(re_segment{ { g.p0.x, g.p0.y, g.p0.z }, { g.p1.x, g.p1.y, g.p1.z }, g.exclude_entity, 0u });
+        const re_box_query_args args{ need_flags, forbid_flags, { 0u, 0u } };
+        std::vector<re_segment_hit> rec(s.size());
+        check(re_query_segments_first(ctx_, s.data(), (uint32_t)s.size(), &args, rec.data(), nullptr), "re_query_segments_first");
+        std::vector<std::optional<re_segment_hit>> first(s.size());
+        for (size_t i = 0; i < rec.size(); i++) if (rec[i].entity_id != RE_SEGMENT_NO_ENTITY) first[i] = rec[i];
+        return first;
+    }
+    std::vector<std::optional<re_sphere_hit>> find_nearest_within_radius(const std::vector<Sphere> &spheres, uint32_t need_flags = 0u, uint32_t forbid_flags = 0u) {
+        upload_if_needed();
+        std::vector<re_sphere> s; s.reserve(spheres.size());
+        for (const Sphere &g : spheres) s.push_back(re_sphere{ { g.centre.x, g.centre.y, g.centre.z }, g.radius, g.exclude_entity, 0u });
+        const re_box_query_args args{ need_flags, forbid_flags, { 0u, 0u } };
+        std::vector<re_sphere_hit> rec(s.size());
+        check(re_query_spheres_nearest(ctx_, s.data(), (uint32_t)s.size(), &args, rec.data(), nullptr), "re_query_spheres_nearest");
+        std::vector<std::optional<re_sphere_hit>> nearest(s.size());
+        for (size_t i = 0; i < rec.size(); i++) if (rec[i].entity_id != RE_SPHERE_NO_ENTITY) nearest[i] = rec[i];
+        return nearest;
+    }
     bool has_component(EntityId e, uint32_t ecs_bit) { upload_if_needed(); uint32_t bits = 0; check(re_ecs_bitset(ctx_, e, &bits), "re_ecs_bitset"); return (bits >> ecs_bit) & 1u; }   // ecs_bit: RE_ECS_BIT_*
     re_ctx *context() { upload_if_needed(); return ctx_; }
 

@@ -78,6 +78,8 @@ extern "C" {
     pub fn re_query_boxes(ctx: *mut ReCtx, boxes6: *const f32 /* [n * 6]: xmin xmax ymin ymax zmin zmax */, n: u32, args: *const ReBoxQueryArgs, hits: *mut ReBoxHit, capacity: u32, n_total: *mut u32) -> c_int;
     pub fn re_query_segments(ctx: *mut ReCtx, segments: *const ReSegment, n: u32, args: *const ReBoxQueryArgs, hits: *mut ReSegmentHit, capacity: u32, n_total: *mut u32) -> c_int;
     pub fn re_query_spheres(ctx: *mut ReCtx, spheres: *const ReSphere, n: u32, args: *const ReBoxQueryArgs, hits: *mut ReSphereHit, capacity: u32, n_total: *mut u32) -> c_int;
+    pub fn re_query_segments_first(ctx: *mut ReCtx, segments: *const ReSegment, n: u32, args: *const ReBoxQueryArgs, first: *mut ReSegmentHit /* [n] */, n_found: *mut u32 /* optional */) -> c_int;
+    pub fn re_query_spheres_nearest(ctx: *mut ReCtx, spheres: *const ReSphere, n: u32, args: *const ReBoxQueryArgs, nearest: *mut ReSphereHit /* [n] */, n_found: *mut u32 /* optional */) -> c_int;
     pub fn re_wait(ctx: *mut ReCtx, vis: *mut ReVisible, tick: *mut ReTickResult) -> c_int;
     pub fn re_copy_visible(ctx: *mut ReCtx, ids: *mut u32, mats: *mut f32, capacity: u32, n_written: *mut u32) -> c_int;
     pub fn re_set_output_buffers(ctx: *mut ReCtx, d_ids: *mut u32, d_mats: *mut f32, capacity: u32) -> c_int;

@@ -80,6 +80,11 @@ struct ListChannel {
 template <class Query> struct QueryFlow {
     Pinned h_q[2]; uint32_t k = 0; DevBuf<Query> d_q; DevBuf<unsigned long long> d_out; ListChannel ch;
 };
+// ... and one kind of reduced tree query (re_query_segments_first, re_query_spheres_nearest): a flow of its own, so that the call interleaves with its sibling, and
+// behind it best[n], the minimum key of every query between the two launches (hit_key, re_kernels.h); winners: the list as the host reads it before the scatter.
+template <class Query> struct ReducedFlow : QueryFlow<Query> {
+    DevBuf<unsigned long long> d_best; std::vector<unsigned long long> winners;
+};
 // Everything the kernels publish to the polling host thread lives in ONE block of mapped, coherent pinned host memory per frame lane
 // (hipHostMallocMapped | hipHostMallocCoherent): the frame result at 0, the speculation word at 128, the tick counters at 256, the
 // InstanceRange table from 8192 on.  (Round 1 used four separate mapped blocks; what made its group table arrive after
@@ -306,6 +311,7 @@ struct re_ctx : DeviceBytes, WorldState {
     std::vector<re_entity_logic> logic_table; std::unordered_map<uint64_t, uint32_t> logic_index;   // TypeIdentifier -> table index
     ListChannel logic;
     QueryFlow<BoxQuery> boxq; QueryFlow<SegQuery> segq; QueryFlow<SphQuery> sphq;      // tree queries (re_query_boxes, re_query_segments, re_query_spheres)
+    ReducedFlow<SegQuery> segfirst; ReducedFlow<SphQuery> sphnear;                     // ... and their reductions (re_query_segments_first, re_query_spheres_nearest)
 };
 
 #define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return (ctx)->fail(RE_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
@@ -4069,18 +4075,21 @@ static uint64_t make_box_query(const float *b, uint32_t outline, uint32_t atomic
     q->ncells = (uint32_t)std::min<uint64_t>(cells, 0xFFFFFFFFull);
     return cells;
 }
-// What the three calls share, from the argument checks to *n_total.  `call`, `plural`, `argument`: the names in the messages; build(i, &q) checks query i and
-// writes its record, or fails naming it; rec_words: 8-byte words of an output record; A: the kernel's argument block with the kernel's own members set.
+// What the tree queries share up to the launch.  `call`, `plural`, `argument`: the names in the messages; buffer_error: what is wrong with the caller's output
+// buffer, or nullptr; build(i, &q) checks query i and writes its record, or fails naming it; rec_words: 8-byte words of an output record; capacity: records the
+// device list must hold; best: the reduced calls' key array, grown to n with the other buffers; A: the kernel's argument block with the kernel's own members set,
+// filled here.  *launch comes back false where there is nothing to launch (n == 0, a world without rows): the answer is empty.
 template <class Query, class KArgs, class Build>
-static int run_tree_query(re_ctx *c, const char *call, const char *plural, const char *argument, QueryFlow<Query> &F, const void *queries, uint32_t n, const re_box_query_args *args,
-                          void *hits, uint32_t capacity, uint32_t *n_total, Build build, uint32_t rec_words, void (*kernel)(KArgs), KArgs A) {
+static int prepare_tree_query(re_ctx *c, const char *call, const char *plural, const char *argument, const char *buffer_error, QueryFlow<Query> &F, const void *queries, uint32_t n,
+                              const re_box_query_args *args, uint32_t *n_out, Build build, uint32_t rec_words, uint64_t capacity, DevBuf<unsigned long long> *best, KArgs &A, bool *launch) {
+    *launch = false;
     if (n > RE_BOX_QUERY_MAX_QUERIES) return c->fail(RE_E_ARG, "%s: %u %s (at most %u a call)", call, n, plural, RE_BOX_QUERY_MAX_QUERIES);
     if (n && !queries) return c->fail(RE_E_ARG, "%s: %s is NULL", call, argument);
-    if (capacity && !hits) return c->fail(RE_E_ARG, "%s: capacity without a buffer", call);
+    if (buffer_error) return c->fail(RE_E_ARG, "%s: %s", call, buffer_error);
     if (args && (args->reserved[0] || args->reserved[1])) return c->fail(RE_E_ARG, "%s: reserved must be 0", call);
     if (!c->h_res) return c->fail(RE_E_STATE, "%s: no world uploaded", call);
     if (c->cfg.outline_length > (1u << 30)) return c->fail(RE_E_UNSUPPORTED, "%s: outline lengths beyond 2^30 are not supported (32-bit cell arithmetic)", call);
-    if (n_total) *n_total = 0;
+    if (n_out) *n_out = 0;
     if (n == 0) return RE_OK;
     // the batch, checked whole before anything is touched: built in the pinned buffer that was not the last call's source (a refused batch is never launched:
     // only what this call has built in full is copied to the device)
@@ -4096,10 +4105,12 @@ static int run_tree_query(re_ctx *c, const char *call, const char *plural, const
     { int rc = F.ch.open(c); if (rc != RE_OK) return rc; }
     const uint32_t cap_dev = (uint32_t)std::min<uint64_t>(capacity, (uint64_t)n * c->n);      // (no more pairs than queries x rows exist)
     const size_t out_words = (size_t)cap_dev * rec_words;
-    if (F.d_q.n < n || !F.d_q.p || F.d_out.n < out_words || !F.d_out.p) {      // a buffer that must grow is replaced only after the stream has drained
+    const bool grow_best = best && (best->n < n || !best->p);
+    if (F.d_q.n < n || !F.d_q.p || F.d_out.n < out_words || !F.d_out.p || grow_best) {      // a buffer that must grow is replaced only after the stream has drained
         HIPCHK(c, sync_stream(st));
         if (F.d_q.n < n || !F.d_q.p) HIPCHK(c, F.d_q.alloc((size_t)n + n / 2, nullptr));
         if (F.d_out.n < out_words || !F.d_out.p) HIPCHK(c, F.d_out.alloc(((size_t)cap_dev + cap_dev / 2) * rec_words, nullptr));
+        if (grow_best) HIPCHK(c, best->alloc((size_t)n + n / 2, nullptr));
     }
     HIPCHK(c, hipMemcpyAsync(F.d_q.p, hq, (size_t)n * sizeof(Query), hipMemcpyHostToDevice, st));
     A.n = n; A.n_sh_chunks = c->nsh ? (c->nsh + BOXQ_THREADS - 1u) / BOXQ_THREADS : 0u;
@@ -4108,12 +4119,59 @@ static int run_tree_query(re_ctx *c, const char *call, const char *plural, const
     A.row_flags = c->d_flags.p; A.row_id = c->d_id.p; A.row_cell = c->d_row_cell.p; A.row_aabb = c->d_aabb.p;
     A.nsh = c->nsh; A.sh_keys = c->d_sh_keys.p; A.sh_nk = c->d_sh_nk.p; A.sh_begin = c->d_sh_begin.p; A.sh_nact = c->d_sh_nact.p; A.sh_nstat = c->d_sh_nstat.p;
     A.hdr = F.ch.hdr.p; A.out = F.d_out.p; A.h_pub = F.ch.d_pub; A.seq = F.ch.next_seq();
-    const uint32_t grid = n + A.n_sh_chunks * ((n + BOXQ_TILE - 1u) / BOXQ_TILE);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(BOXQ_THREADS), 0, st, A);
+    *launch = true;
+    return RE_OK;
+}
+static uint32_t tree_query_grid(uint32_t n, uint32_t n_sh_chunks) { return n + n_sh_chunks * ((n + BOXQ_TILE - 1u) / BOXQ_TILE); }
+
+// What the three calls that report every hit share, from the argument checks to *n_total.
+template <class Query, class KArgs, class Build>
+static int run_tree_query(re_ctx *c, const char *call, const char *plural, const char *argument, QueryFlow<Query> &F, const void *queries, uint32_t n, const re_box_query_args *args,
+                          void *hits, uint32_t capacity, uint32_t *n_total, Build build, uint32_t rec_words, void (*kernel)(KArgs), KArgs A) {
+    bool launch = false;
+    { int rc = prepare_tree_query(c, call, plural, argument, capacity && !hits ? "capacity without a buffer" : nullptr, F, queries, n, args, n_total, build, rec_words, capacity, nullptr, A, &launch); if (rc != RE_OK) return rc; }
+    if (!launch) return RE_OK;
+    hipLaunchKernelGGL(kernel, dim3(tree_query_grid(n, A.n_sh_chunks)), dim3(BOXQ_THREADS), 0, c->stream, A);
     HIPCHK(c, hipGetLastError());
     uint32_t nrec = 0;
     { int rc = F.ch.wait(c, A.seq, &nrec); if (rc != RE_OK) return rc; }
-    return read_out_list(c, nrec, F.d_out.p, rec_words * sizeof(unsigned long long), hits, cap_dev, n_total);
+    return read_out_list(c, nrec, F.d_out.p, rec_words * sizeof(unsigned long long), hits, A.capacity, n_total);
+}
+
+// What the two reduced calls share: of every query the record with the smallest key among those its sibling would report (hit_key: (value, entity id)).  Two
+// launches in the stream and one publication: best[] set to all ones, pass 1 reduces the keys into it, pass 2 walks again with every query shrunk to its best
+// value and lists the winners -- at most one per query --, the host scatters the list into out[] by the record's query index over a prefill of the no-hit
+// record.  Hit: re_segment_hit / re_sphere_hit (the same four words: query, entity id and two value words).
+template <class Hit, class Query, class KArgs, class Build>
+static int run_tree_query_reduced(re_ctx *c, const char *call, const char *plural, const char *argument, const char *result, ReducedFlow<Query> &F, const void *queries, uint32_t n,
+                                  const re_box_query_args *args, Hit *out, uint32_t *n_found, Build build, void (*reduce)(KArgs), void (*pick)(KArgs), KArgs A) {
+    static_assert(sizeof(Hit) == 16, "a record of two 8-byte words");
+    char missing[64]; snprintf(missing, sizeof missing, "%s is NULL", result);
+    bool launch = false;
+    { int rc = prepare_tree_query(c, call, plural, argument, n && !out ? missing : nullptr, F, queries, n, args, n_found, build, 2u, n, &F.d_best, A, &launch); if (rc != RE_OK) return rc; }
+    for (uint32_t i = 0; i < n; i++) { out[i].query = i; out[i].entity_id = 0xFFFFFFFFu; memset((char *)&out[i] + 8, 0, 8); }      // no hit: RE_SEGMENT_NO_ENTITY / RE_SPHERE_NO_ENTITY, the value words zero
+    if (!launch) return RE_OK;
+    hipStream_t st = c->stream;
+    A.best = F.d_best.p;
+    HIPCHK(c, hipMemsetAsync(F.d_best.p, 0xFF, (size_t)n * sizeof(unsigned long long), st));      // HIT_KEY_NONE
+    const uint32_t grid = tree_query_grid(n, A.n_sh_chunks);
+    hipLaunchKernelGGL(reduce, dim3(grid), dim3(BOXQ_THREADS), 0, st, A);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(pick, dim3(grid), dim3(BOXQ_THREADS), 0, st, A);
+    HIPCHK(c, hipGetLastError());
+    uint32_t nrec = 0;
+    { int rc = F.ch.wait(c, A.seq, &nrec); if (rc != RE_OK) return rc; }
+    if (nrec > A.capacity) return c->fail(RE_E_HIP, "%s: %u winners from %u %s (internal error)", call, nrec, n, plural);
+    F.winners.resize((size_t)nrec * 2u);
+    if (nrec) HIPCHK(c, hipMemcpy(F.winners.data(), F.d_out.p, (size_t)nrec * sizeof(Hit), hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < nrec; k++) {
+        Hit h; memcpy(&h, &F.winners[(size_t)k * 2u], sizeof h);
+        if (h.query >= n) return c->fail(RE_E_HIP, "%s: a winner of query %u among %u %s (internal error)", call, h.query, n, plural);
+        if (out[h.query].entity_id != 0xFFFFFFFFu) return c->fail(RE_E_HIP, "%s: a second winner of query %u (entities %u and %u; internal error)", call, h.query, out[h.query].entity_id, h.entity_id);
+        out[h.query] = h;
+    }
+    if (n_found) *n_found = nrec;
+    return RE_OK;
 }
 
 extern "C" int re_query_boxes(re_ctx *c, const float *boxes6, uint32_t n, const re_box_query_args *args, re_box_hit *hits, uint32_t capacity, uint32_t *n_total) try {
@@ -4133,65 +4191,90 @@ extern "C" int re_query_boxes(re_ctx *c, const float *boxes6, uint32_t n, const 
 
 // ... and the entities along a batch of segments (k_segment_query): the same contract, the same record-list protocol on a channel of its own
 static_assert(sizeof(re_segment) == 32 && sizeof(re_segment_hit) == 16 && sizeof(SegQuery) == 64, "record layouts of include/re_hip.h / re_kernels.h");
+// the check of segment i and its record, for `call` (re_query_segments and re_query_segments_first validate alike)
+static int build_segment_query(re_ctx *c, const char *call, const re_segment *segments, uint32_t i, float margin, SegQuery *out) {
+    const re_segment &s = segments[i];
+    if (s.reserved) return c->fail(RE_E_ARG, "%s: segment %u: reserved must be 0", call, i);
+    SegQuery &q = *out;
+    float bb[6];
+    for (int a = 0; a < 3; a++) {
+        float d = s.p1[a] - s.p0[a];
+        if (!std::isfinite(s.p0[a]) || !std::isfinite(s.p1[a]) || !std::isfinite(d)) return c->fail(RE_E_ARG, "%s: segment %u is not finite (an endpoint, or p1 - p0)", call, i);
+        if (std::fabs(d) < std::numeric_limits<float>::min()) d = 0.0f;                             // (the kernel never divides by a subnormal)
+        q.p0[a] = s.p0[a]; q.d[a] = d;
+        bb[2 * a] = std::min(s.p0[a], s.p1[a]) - margin; bb[2 * a + 1] = std::max(s.p0[a], s.p1[a]) + margin;
+    }
+    // the candidate cells are those of the bounding box, inflated by the margin: the slab test accepts t = 1 after rounding for a face a few ulps beyond p1
+    BoxQuery b;
+    const uint64_t cells = make_box_query(bb, c->cfg.outline_length, c->cfg.atomic_length, c->maxlevel, &b);
+    if (cells > RE_BOX_QUERY_MAX_CELLS) return c->fail(RE_E_ARG, "%s: the bounding box of segment %u covers %llu candidate cells (at most %u: about 30 atomic lengths per axis for a diagonal)", call, i, (unsigned long long)cells, RE_BOX_QUERY_MAX_CELLS);
+    q.exclude = s.exclude_entity; q.flags = b.flags; q.ncells = b.ncells; q.pad = 0;
+    for (int a = 0; a < 3; a++) { q.umin[a] = b.umin[a]; q.umax[a] = b.umax[a]; }
+    return RE_OK;
+}
 extern "C" int re_query_segments(re_ctx *c, const re_segment *segments, uint32_t n, const re_box_query_args *args, re_segment_hit *hits, uint32_t capacity, uint32_t *n_total) try {
     if (!c) return RE_E_ARG;
     SegQueryArgs A{};
     A.outline = c->cfg.outline_length; A.margin = segment_query_margin(c->cfg.outline_length);
     const float margin = A.margin;
-    auto build = [&](uint32_t i, SegQuery *out) {
-        const re_segment &s = segments[i];
-        if (s.reserved) return c->fail(RE_E_ARG, "re_query_segments: segment %u: reserved must be 0", i);
-        SegQuery &q = *out;
-        float bb[6];
-        for (int a = 0; a < 3; a++) {
-            float d = s.p1[a] - s.p0[a];
-            if (!std::isfinite(s.p0[a]) || !std::isfinite(s.p1[a]) || !std::isfinite(d)) return c->fail(RE_E_ARG, "re_query_segments: segment %u is not finite (an endpoint, or p1 - p0)", i);
-            if (std::fabs(d) < std::numeric_limits<float>::min()) d = 0.0f;                             // (the kernel never divides by a subnormal)
-            q.p0[a] = s.p0[a]; q.d[a] = d;
-            bb[2 * a] = std::min(s.p0[a], s.p1[a]) - margin; bb[2 * a + 1] = std::max(s.p0[a], s.p1[a]) + margin;
-        }
-        // the candidate cells are those of the bounding box, inflated by the margin: the slab test accepts t = 1 after rounding for a face a few ulps beyond p1
-        BoxQuery b;
-        const uint64_t cells = make_box_query(bb, c->cfg.outline_length, c->cfg.atomic_length, c->maxlevel, &b);
-        if (cells > RE_BOX_QUERY_MAX_CELLS) return c->fail(RE_E_ARG, "re_query_segments: the bounding box of segment %u covers %llu candidate cells (at most %u: about 30 atomic lengths per axis for a diagonal)", i, (unsigned long long)cells, RE_BOX_QUERY_MAX_CELLS);
-        q.exclude = s.exclude_entity; q.flags = b.flags; q.ncells = b.ncells; q.pad = 0;
-        for (int a = 0; a < 3; a++) { q.umin[a] = b.umin[a]; q.umax[a] = b.umax[a]; }
-        return (int)RE_OK;
-    };
+    auto build = [&](uint32_t i, SegQuery *out) { return build_segment_query(c, "re_query_segments", segments, i, margin, out); };
     return run_tree_query(c, "re_query_segments", "segments", "segments", c->segq, segments, n, args, hits, capacity, n_total, build, 2u, k_segment_query, A);
 } RE_ABI_GUARD(c, "re_query_segments")
 
+// ... and of every segment the first hit alone (k_segment_first_reduce, k_segment_first_pick)
+extern "C" int re_query_segments_first(re_ctx *c, const re_segment *segments, uint32_t n, const re_box_query_args *args, re_segment_hit *first, uint32_t *n_found) try {
+    if (!c) return RE_E_ARG;
+    SegBestArgs A{};
+    A.outline = c->cfg.outline_length; A.margin = segment_query_margin(c->cfg.outline_length);
+    const float margin = A.margin;
+    auto build = [&](uint32_t i, SegQuery *out) { return build_segment_query(c, "re_query_segments_first", segments, i, margin, out); };
+    return run_tree_query_reduced(c, "re_query_segments_first", "segments", "segments", "first", c->segfirst, segments, n, args, first, n_found, build, k_segment_first_reduce, k_segment_first_pick, A);
+} RE_ABI_GUARD(c, "re_query_segments_first")
+
 // ... and the entities within a radius of each point of a batch (k_sphere_query): the same contract, a channel of its own
 static_assert(sizeof(re_sphere) == 24 && sizeof(re_sphere_hit) == 16 && sizeof(SphQuery) == 64, "record layouts of include/re_hip.h / re_kernels.h");
+// the check of sphere i and its record, for `call` (re_query_spheres and re_query_spheres_nearest validate alike)
+static int build_sphere_query(re_ctx *c, const char *call, const re_sphere *spheres, uint32_t i, float margin, SphQuery *out) {
+    const float limit = 64.0f * (float)c->cfg.outline_length;
+    const re_sphere &s = spheres[i];
+    if (s.reserved) return c->fail(RE_E_ARG, "%s: sphere %u: reserved must be 0", call, i);
+    if (!std::isfinite(s.radius) || !std::isfinite(s.centre[0]) || !std::isfinite(s.centre[1]) || !std::isfinite(s.centre[2]))
+        return c->fail(RE_E_ARG, "%s: sphere %u is not finite (its centre or its radius)", call, i);
+    if (s.radius < 0.0f) return c->fail(RE_E_ARG, "%s: sphere %u has a negative radius", call, i);
+    // magnitudes of at most outline * 2^7 (with c +- r) keep one ulp at outline * 2^-16, below the margin of outline * 2^-12
+    if (s.radius > limit || std::fabs(s.centre[0]) > limit || std::fabs(s.centre[1]) > limit || std::fabs(s.centre[2]) > limit)
+        return c->fail(RE_E_ARG, "%s: sphere %u lies beyond 64 outline lengths (a centre coordinate or the radius)", call, i);
+    SphQuery &q = *out;
+    float bb[6];
+    for (int a = 0; a < 3; a++) {
+        q.c[a] = s.centre[a];
+        const float lo = s.centre[a] - s.radius, hi = s.centre[a] + s.radius;
+        bb[2 * a] = lo - margin; bb[2 * a + 1] = hi + margin;
+    }
+    q.r2 = s.radius * s.radius;
+    // the candidate cells are those of the bounding cube, inflated by the margin: the rounding of c +- r and of the test stays below it
+    BoxQuery b;
+    const uint64_t cells = make_box_query(bb, c->cfg.outline_length, c->cfg.atomic_length, c->maxlevel, &b);
+    if (cells > RE_BOX_QUERY_MAX_CELLS) return c->fail(RE_E_ARG, "%s: the bounding cube of sphere %u covers %llu candidate cells (at most %u: a radius of 14 atomic lengths passes)", call, i, (unsigned long long)cells, RE_BOX_QUERY_MAX_CELLS);
+    q.exclude = s.exclude_entity; q.flags = b.flags; q.ncells = b.ncells; q.pad[0] = q.pad[1] = q.pad[2] = 0;
+    for (int a = 0; a < 3; a++) { q.umin[a] = b.umin[a]; q.umax[a] = b.umax[a]; }
+    return RE_OK;
+}
 extern "C" int re_query_spheres(re_ctx *c, const re_sphere *spheres, uint32_t n, const re_box_query_args *args, re_sphere_hit *hits, uint32_t capacity, uint32_t *n_total) try {
     if (!c) return RE_E_ARG;
     SphQueryArgs A{};
     A.outline = c->cfg.outline_length; A.margin = segment_query_margin(c->cfg.outline_length);
-    const float margin = A.margin, limit = 64.0f * (float)c->cfg.outline_length;
-    auto build = [&](uint32_t i, SphQuery *out) {
-        const re_sphere &s = spheres[i];
-        if (s.reserved) return c->fail(RE_E_ARG, "re_query_spheres: sphere %u: reserved must be 0", i);
-        if (!std::isfinite(s.radius) || !std::isfinite(s.centre[0]) || !std::isfinite(s.centre[1]) || !std::isfinite(s.centre[2]))
-            return c->fail(RE_E_ARG, "re_query_spheres: sphere %u is not finite (its centre or its radius)", i);
-        if (s.radius < 0.0f) return c->fail(RE_E_ARG, "re_query_spheres: sphere %u has a negative radius", i);
-        // magnitudes of at most outline * 2^7 (with c +- r) keep one ulp at outline * 2^-16, below the margin of outline * 2^-12
-        if (s.radius > limit || std::fabs(s.centre[0]) > limit || std::fabs(s.centre[1]) > limit || std::fabs(s.centre[2]) > limit)
-            return c->fail(RE_E_ARG, "re_query_spheres: sphere %u lies beyond 64 outline lengths (a centre coordinate or the radius)", i);
-        SphQuery &q = *out;
-        float bb[6];
-        for (int a = 0; a < 3; a++) {
-            q.c[a] = s.centre[a];
-            const float lo = s.centre[a] - s.radius, hi = s.centre[a] + s.radius;
-            bb[2 * a] = lo - margin; bb[2 * a + 1] = hi + margin;
-        }
-        q.r2 = s.radius * s.radius;
-        // the candidate cells are those of the bounding cube, inflated by the margin: the rounding of c +- r and of the test stays below it
-        BoxQuery b;
-        const uint64_t cells = make_box_query(bb, c->cfg.outline_length, c->cfg.atomic_length, c->maxlevel, &b);
-        if (cells > RE_BOX_QUERY_MAX_CELLS) return c->fail(RE_E_ARG, "re_query_spheres: the bounding cube of sphere %u covers %llu candidate cells (at most %u: a radius of 14 atomic lengths passes)", i, (unsigned long long)cells, RE_BOX_QUERY_MAX_CELLS);
-        q.exclude = s.exclude_entity; q.flags = b.flags; q.ncells = b.ncells; q.pad[0] = q.pad[1] = q.pad[2] = 0;
-        for (int a = 0; a < 3; a++) { q.umin[a] = b.umin[a]; q.umax[a] = b.umax[a]; }
-        return (int)RE_OK;
-    };
+    const float margin = A.margin;
+    auto build = [&](uint32_t i, SphQuery *out) { return build_sphere_query(c, "re_query_spheres", spheres, i, margin, out); };
     return run_tree_query(c, "re_query_spheres", "spheres", "spheres", c->sphq, spheres, n, args, hits, capacity, n_total, build, 2u, k_sphere_query, A);
 } RE_ABI_GUARD(c, "re_query_spheres")
+
+// ... and of every sphere the nearest entity alone (k_sphere_nearest_reduce, k_sphere_nearest_pick)
+extern "C" int re_query_spheres_nearest(re_ctx *c, const re_sphere *spheres, uint32_t n, const re_box_query_args *args, re_sphere_hit *nearest, uint32_t *n_found) try {
+    if (!c) return RE_E_ARG;
+    SphBestArgs A{};
+    A.outline = c->cfg.outline_length; A.margin = segment_query_margin(c->cfg.outline_length);
+    const float margin = A.margin;
+    auto build = [&](uint32_t i, SphQuery *out) { return build_sphere_query(c, "re_query_spheres_nearest", spheres, i, margin, out); };
+    return run_tree_query_reduced(c, "re_query_spheres_nearest", "spheres", "spheres", "nearest", c->sphnear, spheres, n, args, nearest, n_found, build, k_sphere_nearest_reduce, k_sphere_nearest_pick, A);
+} RE_ABI_GUARD(c, "re_query_spheres_nearest")

@@ -479,6 +479,21 @@ static_assert(sizeof(BoxQueryArgs) == sizeof(TreeQueryHead) + sizeof(BoxQueryOwn
 __global__ void k_box_query(BoxQueryArgs A);
 __global__ void k_segment_query(SegQueryArgs A);
 __global__ void k_sphere_query(SphQueryArgs A);
+// ... and of every segment the first hit, of every sphere the nearest one (re_query_segments_first, re_query_spheres_nearest): the same walk twice, storing
+// differently.  The key of a hit: bits(value) << 32 | entity id, value = t_enter or dist_sq.  Both values are >= +0.0f and never NaN (the slab test's lo
+// starts at +0.0f and is replaced only by something greater; dist_sq is a sum of squares of 0.0f or positive differences), and the bit patterns of
+// non-negative floats order as the floats do, so the unsigned order of the keys is the lexicographic (value, id) order of first_hits / nearest_hits.
+// All ones: no hit (0xFFFFFFFF is no entity's id: it is RE_SEGMENT_NO_ENTITY / RE_SPHERE_NO_ENTITY).
+RE_HD unsigned long long hit_key(uint32_t value_bits, uint32_t id) { return ((unsigned long long)value_bits << 32) | id; }
+constexpr unsigned long long HIT_KEY_NONE = ~0ull;
+// the argument blocks: the sibling's, and behind it best[n] -- pass 1 (reduce) takes the minimum key of every query into it, pass 2 (pick) walks again with
+// every query shrunk to its best value and stores the record whose key equals best[query]
+struct SegBestArgs : SegQueryArgs { unsigned long long *best; };
+struct SphBestArgs : SphQueryArgs { unsigned long long *best; };
+__global__ void k_segment_first_reduce(SegBestArgs A);
+__global__ void k_segment_first_pick(SegBestArgs A);
+__global__ void k_sphere_nearest_reduce(SphBestArgs A);
+__global__ void k_sphere_nearest_pick(SphBestArgs A);
 hipError_t sort_pairs_u64_u32(void *tmp, size_t *tmp_bytes, const uint64_t *keys_in, uint64_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out,
                               uint32_t n, unsigned begin_bit, unsigned end_bit, hipStream_t stream);      // re_sort.hip (rocPRIM radix sort)
 __global__ void k_rb_ovl_insert(uint32_t n, const Pair64 *pairs, RbTables T);

@@ -2,7 +2,8 @@
 // (exports/logic_components.rs:14-18) reads out of its &BoundingBoxTree (find_all_unique_world_section_ids, stored_entities_indexes,
 // shared_section_indexes): "who is near this box" (k_box_query), "who lies along this segment" -- a shot, a line of sight, a pick ray (k_segment_query) --
 // and "who is within r of this point" -- an explosion, a proximity trigger (k_sphere_query).
-// One walk of the tree, written once over a query shape; the three kernels instantiate it.
+// One walk of the tree, written once over a query shape and a mode of storing hits; the three kernels instantiate it with the default mode (every hit a record), and
+// the four kernels of re_query_segments_first / re_query_spheres_nearest with the other two: reduce the hits' keys per query, then pick the winners (TreeqMode, below).
 //
 // The rule of the boxes: (query i, entity) for every live entity in the tree (not F_DEAD, not an F_PHANTOM replica, row_cell set; ghost instances of the
 // frozen static cache are no entities) whose stored StaticAABB intersects box i by StaticAABB::intersect (aabb.rs:68-73: closed intervals, plain f32
@@ -35,6 +36,7 @@
 //   cell_box / misses                 the prune of a candidate cell and of a shared section's bounding cell box ([c0, c1] per axis in world units)
 //   test                              the exact test on a row's AABB and id, which fills the record
 //   store                             the record's write-through store below the capacity
+//   value_bits / misses_beyond        (segments, spheres) the value of a record's key -- t_enter, dist_sq --, and the prune of the pick pass: the query shrunk to its best value
 #include "re_kernels.h"
 
 namespace re {
@@ -134,6 +136,15 @@ struct SegShape {
         if (rec.id == exclude) return false;
         return segq_slab(p0[0], p0[1], p0[2], d[0], d[1], d[2], a.xmin, a.xmax, a.ymin, a.ymax, a.zmin, a.zmax, rec.t0, rec.t1);
     }
+    // first hit: the value of a record's key, and the prune of the pick pass -- a cell whose slab lo exceeds the best t_enter holds neither the winner nor
+    // anything tied with it.  Per axis with d > 0 the cell's near bound mn is no greater than the entity's, and (mn - p) / d is monotone in mn (f32 subtract
+    // and divide by a positive number keep order; mirrored for d < 0 with the far bound; d == 0 adds nothing to lo); the maximum over the axes keeps the
+    // order: lo(cell) <= t_enter(entity).
+    static __device__ __forceinline__ uint32_t value_bits(const Rec &r) { return __float_as_uint(r.t0); }
+    __device__ __forceinline__ bool misses_beyond(const CellBox &b, float best) const {
+        float t0, t1;
+        return !segq_slab(p0[0], p0[1], p0[2], d[0], d[1], d[2], b.x0, b.x1, b.y0, b.y1, b.z0, b.z1, t0, t1) || t0 > best;
+    }
     // write-through stores, as the box query's; two 8-byte halves, both below the capacity or neither
     static __device__ __forceinline__ void store(const Args &A, uint32_t slot, const Rec &r) {
         if (slot >= A.capacity) return;
@@ -197,6 +208,14 @@ struct SphShape {
         rec.dist_sq = sphq_dist_sq(c, a.xmin, a.xmax, a.ymin, a.ymax, a.zmin, a.zmax, rec.side);
         return rec.dist_sq <= r2;
     }
+    // nearest: the value of a record's key, and the prune of the pick pass -- the prune above with r2 := the best dist_sq (its monotonicity argument holds for
+    // any bound: dist_sq(cell) <= dist_sq(entity), so a cell further away than the best holds neither the winner nor anything tied with it)
+    static __device__ __forceinline__ uint32_t value_bits(const Rec &r) { return __float_as_uint(r.dist_sq); }
+    __device__ __forceinline__ bool misses_beyond(const CellBox &b, float best) const {
+        SphShape P = *this;
+        P.r2 = best;
+        return P.misses(b);
+    }
     // write-through stores, as the segment query's; two 8-byte halves, both below the capacity or neither
     static __device__ __forceinline__ void store(const Args &A, uint32_t slot, const Rec &r) {
         if (slot >= A.capacity) return;
@@ -209,8 +228,28 @@ struct SphShape {
 // ---- the walk ---------------------------------------------------------------------------------------------------------------------------------------
 constexpr uint32_t TREEQ_TILE_HEAD = 7;        // every shape's tile entry starts with umin[3], umax[3], flags; the shape's payload follows
 
-template <class Shape> struct TreeqShared {
-    typename Shape::Rec hits[BOXQ_HITBUF];         // staged records
+// What the walk does with a hit (a mode beside the shape; the argument block of the two new modes carries best[n] behind the sibling's members):
+//   TREEQ_ALL     every hit is a record: staged in LDS, flushed into the list, the launch signs off (the three queries above)
+//   TREEQ_REDUCE  pass 1 of first hit / nearest: no record -- the hit's key (hit_key, re_kernels.h) is reduced into best[query]: a wave minimum and one LDS
+//                 atomicMin per wave iteration in the row walk, one LDS atomicMin per hit in the shared part, one global atomicMin per workgroup and query
+//                 that found anything.  Counts nothing, does not touch the header, does not sign off.
+//   TREEQ_PICK    pass 2: every query shrunk to its best value (Shape::misses_beyond), a query without a hit walks nothing; the one hit whose key equals
+//                 best[query] is a record and leaves as in TREEQ_ALL.  Entity ids are unique and the rule yields each pair once: one record per query with a hit.
+enum TreeqMode { TREEQ_ALL = 0, TREEQ_REDUCE = 1, TREEQ_PICK = 2 };
+
+template <class Shape, int Mode> struct TreeqStore {                     // TREEQ_ALL
+    static constexpr uint32_t NHIT = BOXQ_HITBUF;
+    typename Shape::Rec hits[NHIT];                // staged records
+};
+template <class Shape> struct TreeqStore<Shape, TREEQ_REDUCE> {          // no staging buffer: its LDS is free
+    unsigned long long best[BOXQ_TILE];            // unique part: [0] the workgroup's own best key; shared part: the best key of every tile query
+};
+template <class Shape> struct TreeqStore<Shape, TREEQ_PICK> {
+    static constexpr uint32_t NHIT = BOXQ_TILE;    // (a workgroup keeps at most one record per query: one in the unique part, one per tile query in the shared part)
+    typename Shape::Rec hits[NHIT];
+    unsigned long long best[BOXQ_TILE];            // shared part: best[q0 + i] of every tile query
+};
+template <class Shape, int Mode = TREEQ_ALL> struct TreeqShared : TreeqStore<Shape, Mode> {
     uint32_t queue[BOXQ_TILE * Shape::TILE_WORDS]; // unique part: slots of the hit sections of a round; shared part: the query tile
     uint32_t n_hits, n_queue, gbase;
     uint32_t prefix[MAX_LEVELS + 2], lo[3][MAX_LEVELS + 1], ext[3][MAX_LEVELS + 1];      // unique part: candidate cells before each level, first cell and extent per axis
@@ -219,9 +258,9 @@ template <class Shape> struct TreeqShared {
 };
 
 // the staged records leave: ONE global atomicAdd per workgroup and flush.  Called by all 256 threads.
-template <class Shape> __device__ __forceinline__ void treeq_flush(const typename Shape::Args &A, TreeqShared<Shape> &S) {
+template <class Shape, int Mode> __device__ __forceinline__ void treeq_flush(const typename Shape::Args &A, TreeqShared<Shape, Mode> &S) {
     __syncthreads();
-    const uint32_t n = S.n_hits < BOXQ_HITBUF ? S.n_hits : BOXQ_HITBUF;
+    const uint32_t n = S.n_hits < S.NHIT ? S.n_hits : S.NHIT;
     if (n == 0u) return;                                                   // (uniform)
     if (threadIdx.x == 0) S.gbase = atomicAdd(&A.hdr->count, n);
     __syncthreads();
@@ -242,32 +281,60 @@ template <class Shape> __device__ __forceinline__ bool treeq_row_hit(const typen
     return treeq_row_live(A, r, expect) && P.test(A.row_aabb[r], &A.row_id[r], query, rec);
 }
 
-// one wave walks rows[begin .. begin + cnt): one lane per row, ballot + mbcnt compaction into the workgroup's staging buffer
-template <class Shape> __device__ __forceinline__ void treeq_walk_wave(const typename Shape::Args &A, TreeqShared<Shape> &S, const Shape &P, uint32_t query, uint32_t begin, uint32_t cnt, uint32_t expect) {
+template <class Shape> __device__ __forceinline__ unsigned long long treeq_key(const typename Shape::Rec &rec) { return hit_key(Shape::value_bits(rec), rec.id); }
+__device__ __forceinline__ float treeq_key_value(unsigned long long key) { return __uint_as_float((uint32_t)(key >> 32)); }
+// the minimum of a 64-bit key over the lanes of a wave, by shuffles (every lane ends with it)
+__device__ __forceinline__ unsigned long long treeq_wave_min(unsigned long long k) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = ((unsigned long long)__shfl_xor((uint32_t)(k >> 32), off) << 32) | __shfl_xor((uint32_t)k, off);
+        k = o < k ? o : k;
+    }
+    return k;
+}
+
+// the hits of one wave iteration go into the workgroup's staging buffer: ballot + mbcnt compaction
+template <class Shape, int Mode> __device__ __forceinline__ void treeq_stage_wave(const typename Shape::Args &A, TreeqShared<Shape, Mode> &S, bool hit, const typename Shape::Rec &rec, uint64_t mask, uint32_t lane) {
+    uint32_t pos = 0;
+    if (lane == 0u) pos = atomicAdd(&S.n_hits, (uint32_t)__popcll(mask));
+    pos = __shfl(pos, 0) + treeq_mbcnt(mask);
+    if (hit && pos < S.NHIT) S.hits[pos] = rec;
+    const uint64_t over = __ballot(hit && pos >= S.NHIT);                  // the staging buffer is full: this wave's remainder goes out directly
+    if (over) {
+        uint32_t g = 0;
+        if (lane == 0u) g = atomicAdd(&A.hdr->count, (uint32_t)__popcll(over));
+        g = __shfl(g, 0) + treeq_mbcnt(over);
+        if (hit && pos >= S.NHIT) Shape::store(A, g, rec);
+    }
+}
+
+// one wave walks rows[begin .. begin + cnt): one lane per row
+// (bk: TREEQ_PICK: the query's best key, the only one kept.  TREEQ_REDUCE: every lane holds the same query, so the wave's minimum goes into the workgroup's best)
+template <class Shape, int Mode> __device__ __forceinline__ void treeq_walk_wave(const typename Shape::Args &A, TreeqShared<Shape, Mode> &S, const Shape &P, uint32_t query, uint32_t begin, uint32_t cnt, uint32_t expect,
+                                                                                 unsigned long long bk) {
     const uint32_t lane = threadIdx.x & 63u;
     for (uint32_t base = 0; base < cnt; base += 64u) {                     // (wave-uniform trip count)
         const uint32_t k = base + lane;
         typename Shape::Rec rec{};
         bool hit = false;
         if (k < cnt) hit = treeq_row_hit(A, P, A.rows[begin + k], expect, query, rec);
+        if constexpr (Mode == TREEQ_PICK) hit = hit && treeq_key<Shape>(rec) == bk;
         const uint64_t mask = __ballot(hit);
         if (!mask) continue;
-        uint32_t pos = 0;
-        if (lane == 0u) pos = atomicAdd(&S.n_hits, (uint32_t)__popcll(mask));
-        pos = __shfl(pos, 0) + treeq_mbcnt(mask);
-        if (hit && pos < BOXQ_HITBUF) S.hits[pos] = rec;
-        const uint64_t over = __ballot(hit && pos >= BOXQ_HITBUF);        // the staging buffer is full: this wave's remainder goes out directly
-        if (over) {
-            uint32_t g = 0;
-            if (lane == 0u) g = atomicAdd(&A.hdr->count, (uint32_t)__popcll(over));
-            g = __shfl(g, 0) + treeq_mbcnt(over);
-            if (hit && pos >= BOXQ_HITBUF) Shape::store(A, g, rec);
-        }
+        if constexpr (Mode == TREEQ_REDUCE) {
+            const unsigned long long m = treeq_wave_min(hit ? treeq_key<Shape>(rec) : HIT_KEY_NONE);
+            if (lane == 0u) atomicMin(&S.best[0], m);
+        } else treeq_stage_wave(A, S, hit, rec, mask, lane);
     }
 }
 
-template <class Shape> __device__ __forceinline__ void treeq_unique_part(const typename Shape::Args &A, TreeqShared<Shape> &S) {
+template <class Shape, int Mode, class KArgs> __device__ __forceinline__ void treeq_unique_part(const KArgs &A, TreeqShared<Shape, Mode> &S) {
     const uint32_t tid = threadIdx.x, wave = tid >> 6, query = blockIdx.x;
+    unsigned long long bk = HIT_KEY_NONE;
+    if constexpr (Mode == TREEQ_PICK) {
+        bk = A.best[query];                                                // (pass 1 has ended: the launches follow each other in the stream)
+        if (bk == HIT_KEY_NONE) return;                                    // (uniform) no hit: nothing to walk, the workgroup still signs off
+    }
     const typename Shape::Query &Q = A.q[query];
     const uint32_t nlev = A.max_level + 1u;                                // an entity longer than half the outline sits at level max_level
     Shape::stage(S.own, Q, tid);
@@ -297,7 +364,8 @@ template <class Shape> __device__ __forceinline__ void treeq_unique_part(const t
             const uint32_t ix = idx % nx, rest = idx / nx, iy = rest % ny, iz = rest / ny;
             const uint32_t cx = S.lo[0][l] + ix, cy = S.lo[1][l] + iy, cz = S.lo[2][l] + iz, len = A.atomic << l;
             const uint32_t c0[3] = { cx * len, cy * len, cz * len }, c1[3] = { cx * len + len, cy * len + len, cz * len + len };
-            if (P.misses(Shape::cell_box(A, c0, c1))) continue;
+            if constexpr (Mode == TREEQ_PICK) { if (P.misses_beyond(Shape::cell_box(A, c0, c1), treeq_key_value(bk))) continue; }
+            else if (P.misses(Shape::cell_box(A, c0, c1))) continue;
             const uint64_t key = pack_key(l, cx, cz, cy);
             const int32_t slot = rb_find(A.T, A.cell_key, key);
             if (slot >= 0 && A.cell_nl[slot] + A.cell_ns[slot] != 0u) S.queue[atomicAdd(&S.n_queue, 1u)] = (uint32_t)slot;
@@ -306,11 +374,14 @@ template <class Shape> __device__ __forceinline__ void treeq_unique_part(const t
         const uint32_t nq = S.n_queue;
         for (uint32_t e = wave; e < nq; e += BOXQ_THREADS / 64u) {          // one wave per hit section: active rows, then static rows; the ghost tail is not walked
             const uint32_t slot = S.queue[e];
-            treeq_walk_wave(A, S, P, query, A.cell_begin[slot], A.cell_nl[slot] + A.cell_ns[slot], slot);
+            treeq_walk_wave(A, S, P, query, A.cell_begin[slot], A.cell_nl[slot] + A.cell_ns[slot], slot, bk);
         }
-        treeq_flush(A, S);
+        if constexpr (Mode == TREEQ_REDUCE) __syncthreads(); else treeq_flush<Shape, Mode>(A, S);
         if (tid == 0) S.n_queue = 0u;
         __syncthreads();
+    }
+    if constexpr (Mode == TREEQ_REDUCE) {                                  // (the barrier above: every wave's LDS minimum is in)
+        if (tid == 0 && S.best[0] != HIT_KEY_NONE) atomicMin(&A.best[query], S.best[0]);      // ONE global atomic, only if the workgroup found anything
     }
 }
 
@@ -325,7 +396,7 @@ __device__ __forceinline__ bool treeq_cells_in_range(const uint32_t *c0, const u
            treeq_cell_in_range(c0[2], c1[2], t[2], t[5], (fl >> 2) & 1u);
 }
 
-template <class Shape> __device__ __forceinline__ void treeq_shared_part(const typename Shape::Args &A, TreeqShared<Shape> &S) {
+template <class Shape, int Mode, class KArgs> __device__ __forceinline__ void treeq_shared_part(const KArgs &A, TreeqShared<Shape, Mode> &S) {
     const uint32_t tid = threadIdx.x, sb = blockIdx.x - A.n;
     const uint32_t chunk = sb % A.n_sh_chunks, q0 = (sb / A.n_sh_chunks) * BOXQ_TILE;
     const uint32_t nq = A.n - q0 < BOXQ_TILE ? A.n - q0 : BOXQ_TILE;
@@ -336,6 +407,7 @@ template <class Shape> __device__ __forceinline__ void treeq_shared_part(const t
         for (uint32_t a = 0; a < 3u; a++) { t[a] = Q.umin[a]; t[3u + a] = Q.umax[a]; }
         t[6] = Q.flags;
         Shape::to_tile(Q, t + TREEQ_TILE_HEAD);
+        if constexpr (Mode == TREEQ_PICK) S.best[tid] = A.best[q0 + tid];
     }
     __syncthreads();
     const uint32_t s = chunk * BOXQ_THREADS + tid;
@@ -364,6 +436,8 @@ template <class Shape> __device__ __forceinline__ void treeq_shared_part(const t
         Aabb a0 = {}; uint32_t id0 = 0;
         if (r0 < A.nrows) { a0 = A.row_aabb[r0]; id0 = A.row_id[r0]; }
         for (uint32_t i = 0; i < nq; i++) {
+            unsigned long long bk = HIT_KEY_NONE;
+            if constexpr (Mode == TREEQ_PICK) { bk = S.best[i]; if (bk == HIT_KEY_NONE) continue; }      // a tile entry without a hit walks nothing
             const uint32_t *t = tile + i * Shape::TILE_WORDS;
             if (!treeq_cells_in_range(b0, b1, t)) continue;
             bool any = false;
@@ -376,37 +450,53 @@ template <class Shape> __device__ __forceinline__ void treeq_shared_part(const t
                 }
             if (!any) continue;
             const Shape P = Shape::from_tile(t + TREEQ_TILE_HEAD);
-            if (P.misses(bound)) continue;
+            if constexpr (Mode == TREEQ_PICK) { if (P.misses_beyond(bound, treeq_key_value(bk))) continue; }
+            else if (P.misses(bound)) continue;
             // walked ONCE for this query, however many of its linked keys lie in the range
             for (uint32_t m = 0; m < cnt; m++) {
                 typename Shape::Rec rec{};
                 if (m == 0u ? !(live0 && P.test(a0, &id0, q0 + i, rec)) : !treeq_row_hit(A, P, A.rows[begin + m], expect, q0 + i, rec)) continue;
-                const uint32_t pos = atomicAdd(&S.n_hits, 1u);
-                if (pos < BOXQ_HITBUF) S.hits[pos] = rec;
-                else Shape::store(A, atomicAdd(&A.hdr->count, 1u), rec);
+                if constexpr (Mode == TREEQ_REDUCE) atomicMin(&S.best[i], treeq_key<Shape>(rec));
+                else {
+                    if constexpr (Mode == TREEQ_PICK) { if (treeq_key<Shape>(rec) != bk) continue; }
+                    const uint32_t pos = atomicAdd(&S.n_hits, 1u);
+                    if (pos < S.NHIT) S.hits[pos] = rec;
+                    else Shape::store(A, atomicAdd(&A.hdr->count, 1u), rec);
+                }
             }
         }
     }
-    treeq_flush(A, S);
+    if constexpr (Mode == TREEQ_REDUCE) {
+        __syncthreads();
+        if (tid < nq && S.best[tid] != HIT_KEY_NONE) atomicMin(&A.best[q0 + tid], S.best[tid]);      // one global atomic per tile query that has a key
+    } else treeq_flush<Shape, Mode>(A, S);
 }
 
 // Grid: workgroups [0, n) take one query each through the unique sections; the workgroups behind them take (256 shared sections) x (256 queries) each.
 // 256 threads, 64-wide waves, no recursion; every loop is bounded (candidate cells by the host's cap, rb_find's probe by an empty slot of an overlay that is
 // never full and a binary search, the row walks by the sections' counts).
 // Publication: write-through records, every wave waits for its own stores, then the workgroup signs off (list_sign_off, re_kernels.h).
-template <class Shape> __device__ __forceinline__ void treeq_kernel(const typename Shape::Args &A, TreeqShared<Shape> &S) {
+template <class Shape, int Mode = TREEQ_ALL, class KArgs> __device__ __forceinline__ void treeq_kernel(const KArgs &A, TreeqShared<Shape, Mode> &S) {
     if (threadIdx.x == 0) { S.n_hits = 0u; S.n_queue = 0u; }
+    if constexpr (Mode == TREEQ_REDUCE) S.best[threadIdx.x] = HIT_KEY_NONE;      // (BOXQ_TILE == BOXQ_THREADS)
     __syncthreads();
-    if (blockIdx.x < A.n) treeq_unique_part(A, S); else treeq_shared_part(A, S);
+    if (blockIdx.x < A.n) treeq_unique_part<Shape, Mode>(A, S); else treeq_shared_part<Shape, Mode>(A, S);
+    if constexpr (Mode == TREEQ_REDUCE) return;                               // nothing counted, nothing published: the pick pass answers
     wait_own_stores();
     __syncthreads();                                                          // every wave's records have left; the count atomics have returned
     if (threadIdx.x == 0) list_sign_off(A.hdr, A.h_pub, A.seq);
 }
+static_assert(BOXQ_TILE == BOXQ_THREADS, "one lane per tile query");
 
 }  // namespace
 
-__global__ __launch_bounds__(BOXQ_THREADS) void k_box_query(BoxQueryArgs A) { __shared__ TreeqShared<BoxShape> S; treeq_kernel(A, S); }
-__global__ __launch_bounds__(BOXQ_THREADS) void k_segment_query(SegQueryArgs A) { __shared__ TreeqShared<SegShape> S; treeq_kernel(A, S); }
-__global__ __launch_bounds__(BOXQ_THREADS) void k_sphere_query(SphQueryArgs A) { __shared__ TreeqShared<SphShape> S; treeq_kernel(A, S); }
+__global__ __launch_bounds__(BOXQ_THREADS) void k_box_query(BoxQueryArgs A) { __shared__ TreeqShared<BoxShape> S; treeq_kernel<BoxShape>(A, S); }
+__global__ __launch_bounds__(BOXQ_THREADS) void k_segment_query(SegQueryArgs A) { __shared__ TreeqShared<SegShape> S; treeq_kernel<SegShape>(A, S); }
+__global__ __launch_bounds__(BOXQ_THREADS) void k_sphere_query(SphQueryArgs A) { __shared__ TreeqShared<SphShape> S; treeq_kernel<SphShape>(A, S); }
+// first hit per segment, nearest per sphere: reduce, then pick (two launches in the stream, no host round trip between them)
+__global__ __launch_bounds__(BOXQ_THREADS) void k_segment_first_reduce(SegBestArgs A) { __shared__ TreeqShared<SegShape, TREEQ_REDUCE> S; treeq_kernel<SegShape, TREEQ_REDUCE>(A, S); }
+__global__ __launch_bounds__(BOXQ_THREADS) void k_segment_first_pick(SegBestArgs A) { __shared__ TreeqShared<SegShape, TREEQ_PICK> S; treeq_kernel<SegShape, TREEQ_PICK>(A, S); }
+__global__ __launch_bounds__(BOXQ_THREADS) void k_sphere_nearest_reduce(SphBestArgs A) { __shared__ TreeqShared<SphShape, TREEQ_REDUCE> S; treeq_kernel<SphShape, TREEQ_REDUCE>(A, S); }
+__global__ __launch_bounds__(BOXQ_THREADS) void k_sphere_nearest_pick(SphBestArgs A) { __shared__ TreeqShared<SphShape, TREEQ_PICK> S; treeq_kernel<SphShape, TREEQ_PICK>(A, S); }
 
 }  // namespace re

@@ -454,6 +454,48 @@ class Pipeline:
         args = _capi.BoxQueryArgs(int(need_flags), int(forbid_flags)) if (need_flags or forbid_flags) else None
         return self._record_list(self._L.re_query_spheres, (sph.ctypes.data, len(sph), args), "re_query_spheres", capacity, _capi.SPHERE_HIT_DT)
 
+    def _reduced_query(self, fn, name, batch, need, forbid, dtype):
+        """the reduced tree queries fn(ctx, queries, n, args, out[n], &n_found): (records, found) in the format of first_hits / nearest_hits"""
+        args = _capi.BoxQueryArgs(int(need), int(forbid)) if (need or forbid) else None
+        n = len(batch)
+        rec = np.zeros(max(n, 1), dtype)
+        n_found = C.c_uint32()
+        self._check(fn(self._h, batch.ctypes.data, n, args, rec.ctypes.data, C.byref(n_found)), name)
+        rec = rec[:n].copy()
+        found = rec["entity_id"] != 0xFFFFFFFF
+        rec["entity_id"][~found] = 0                 # first_hits / nearest_hits leave a query without a hit zero but for its index
+        if int(found.sum()) != n_found.value:
+            raise RenderEngineError(f"{name}: n_found {n_found.value} against {int(found.sum())} records with an entity")
+        return rec, found
+
+    def find_first_along_segments(self, segments, exclude=None, need=0, forbid=0):
+        """what each segment of a batch hits first, reduced on the device (re_query_segments_first): (first, found) exactly as
+        first_hits(find_entities_along_segments(segments, exclude, need, forbid)[0], n) gives them -- first[i] the record of segment i with the smallest
+        (t_enter, entity_id), bit for bit; found[i] False and first[i] zero but for its query index where it hit nothing.  16 bytes a segment come back
+        instead of every hit.  Valid at any point between calls."""
+        if isinstance(segments, np.ndarray) and segments.dtype == _capi.SEGMENT_DT:
+            seg = np.ascontiguousarray(segments)
+        else:
+            pts = np.ascontiguousarray(segments, np.float32).reshape(-1, 6)
+            seg = np.zeros(len(pts), _capi.SEGMENT_DT)
+            seg["p0"], seg["p1"] = pts[:, 0:3], pts[:, 3:6]
+            seg["exclude_entity"] = _capi.SEGMENT_NO_ENTITY if exclude is None else np.asarray(exclude, np.uint32)
+        return self._reduced_query(self._L.re_query_segments_first, "re_query_segments_first", seg, need, forbid, _capi.SEGMENT_HIT_DT)
+
+    def find_nearest_within_radius(self, spheres, exclude=None, need=0, forbid=0):
+        """the entity nearest to each point of a batch within its radius, reduced on the device (re_query_spheres_nearest): (nearest, found) exactly as
+        nearest_hits(find_entities_within_radius(spheres, exclude, need, forbid)[0], n) gives them -- nearest[i] the record of sphere i with the smallest
+        (dist_sq, entity_id), bit for bit; found[i] False and nearest[i] zero but for its query index where nothing lies within the radius.  Valid at any
+        point between calls."""
+        if isinstance(spheres, np.ndarray) and spheres.dtype == _capi.SPHERE_DT:
+            sph = np.ascontiguousarray(spheres)
+        else:
+            pts = np.ascontiguousarray(spheres, np.float32).reshape(-1, 4)
+            sph = np.zeros(len(pts), _capi.SPHERE_DT)
+            sph["centre"], sph["radius"] = pts[:, 0:3], pts[:, 3]
+            sph["exclude_entity"] = _capi.SPHERE_NO_ENTITY if exclude is None else np.asarray(exclude, np.uint32)
+        return self._reduced_query(self._L.re_query_spheres_nearest, "re_query_spheres_nearest", sph, need, forbid, _capi.SPHERE_HIT_DT)
+
     # -- multi-GPU exchange (RCCL behind the C ABI) ---------------------------------------------------
     @staticmethod
     def comm_unique_id():
