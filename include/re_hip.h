@@ -462,6 +462,36 @@ int re_query_segments_first (re_ctx *ctx, const re_segment *segments, uint32_t n
 int re_query_spheres_nearest(re_ctx *ctx, const re_sphere  *spheres,  uint32_t n, const re_box_query_args *args,
                              re_sphere_hit  *nearest /* [n] */, uint32_t *n_found /* optional */);
 
+/* The same two questions asked by entity: "who is within `reach` of me".  A logic callback asks about an entity, not about geometry, and the entity's
+ * current StaticAABB and Position exist on the device only (re_tick and the re-bucket move them there): instead of one re_read_component round trip per
+ * asker, the caller sends entity ids and a reach, a small kernel builds the query records from the entities' state as it is when the call runs (an
+ * asynchronous cull or tick in flight is finished first), and the sibling's walk answers them in the same stream: one call, one publication.
+ *   re_query_boxes_around: query i is the box (min - reach, max + reach) per axis of the asker's stored StaticAABB (RE_C_STATIC_AABB), every bound one
+ *     plain f32 subtraction / addition.  The answer is exactly what re_query_boxes reports for that box, args filters included, minus the asker itself;
+ *     with RE_AROUND_INCLUDE_SELF the asker is kept (when the filters let it through).
+ *   re_query_spheres_around: query i is the sphere with centre = the asker's Position (RE_C_POSITION) and radius = reach.  The answer is exactly what
+ *     re_query_spheres reports for { centre, radius, exclude_entity = the asker }, dist_sq and side bit for bit; with RE_AROUND_INCLUDE_SELF,
+ *     exclude_entity is RE_SPHERE_NO_ENTITY.
+ * status (nullable, one byte a query), decided on the device: RE_AROUND_NOT_IN_TREE and no hits for an asker that is not in the tree (no section, or an
+ * RE_F_PHANTOM halo replica, where the owner answers); RE_AROUND_TOO_LARGE and no hits for a query whose candidate world sections exceed
+ * RE_BOX_QUERY_MAX_CELLS (or, spheres, whose centre lies beyond 64 outline lengths).  The other queries of the batch are answered and the call returns
+ * RE_OK.  This differs from the siblings, which refuse such a batch with RE_E_ARG: here the host cannot know the box before the launch.
+ * RE_E_ARG before any launch (the message names the first offending ask, the whole batch is checked before anything is touched): an unknown or removed
+ * entity, a NaN, infinite or negative reach (spheres: a reach above 64 outline lengths), unknown flag bits, nonzero reserved; and the siblings':
+ * n > RE_BOX_QUERY_MAX_QUERIES, asks == NULL with n > 0, capacity without a buffer, nonzero reserved words of args.  RE_E_STATE before any upload.
+ * RE_E_UNSUPPORTED for an outline beyond 2^30.  n == 0, or a world without entities: no hits.  *n_total, capacity and hits as re_query_boxes: *n_total is
+ * exact even with capacity == 0, the first `capacity` records are written.  The same entity may ask more than once in a batch. */
+typedef struct { uint32_t entity_id; float reach; uint32_t flags /* RE_AROUND_INCLUDE_SELF or 0 */, reserved /* 0 */; } re_around;   /* 16 bytes */
+#define RE_AROUND_INCLUDE_SELF 1u
+/* status[i], one byte a query */
+#define RE_AROUND_OK 0u
+#define RE_AROUND_NOT_IN_TREE 1u
+#define RE_AROUND_TOO_LARGE 2u
+int re_query_boxes_around  (re_ctx *ctx, const re_around *asks, uint32_t n, const re_box_query_args *args,
+                            re_box_hit *hits, uint32_t capacity, uint32_t *n_total, uint8_t *status /* nullable, [n] */);
+int re_query_spheres_around(re_ctx *ctx, const re_around *asks, uint32_t n, const re_box_query_args *args,
+                            re_sphere_hit *hits, uint32_t capacity, uint32_t *n_total, uint8_t *status /* nullable, [n] */);
+
 /* ECS read-back for user logic (LogicFunction reads components through &ECS, exports/logic_components.rs:15-18).  A component the entity does not
  * carry (never written, or removed by RE_CHANGE_REMOVE_COMPONENT) yields RE_E_ARG == ECS::get_copy -> None (objects/ecs.rs:653-664). */
 int re_read_component(re_ctx *ctx, uint32_t entity_id, int component, void *dst);

@@ -477,6 +477,17 @@ class Pipeline {
         for (size_t i = 0; i < rec.size(); i++) if (rec[i].entity_id != RE_SPHERE_NO_ENTITY) nearest[i] = rec[i];
         return nearest;
     }
+    // ... and the same two questions asked by entity (re_query_boxes_around, re_query_spheres_around): who is within `reach` of each asker's StaticAABB / of its
+    // Position, from the askers' state on the device as it is now -- no get_copy of their components.  The asker is left out unless include_self.  status[i]:
+    // RE_AROUND_OK, or RE_AROUND_NOT_IN_TREE / RE_AROUND_TOO_LARGE and no hits for that asker alone.
+    struct Around { EntityId entity; float reach = 0.0f; bool include_self = false; };
+    template <class Hit> struct AroundAnswer { std::vector<Hit> hits; std::vector<uint8_t> status; };
+    AroundAnswer<re_box_hit> find_entities_around(const std::vector<Around> &asks, uint32_t need_flags = 0u, uint32_t forbid_flags = 0u) {
+        return around_query<re_box_hit>(re_query_boxes_around, "re_query_boxes_around", asks, need_flags, forbid_flags);
+    }
+    AroundAnswer<re_sphere_hit> find_entities_within_reach(const std::vector<Around> &asks, uint32_t need_flags = 0u, uint32_t forbid_flags = 0u) {
+        return around_query<re_sphere_hit>(re_query_spheres_around, "re_query_spheres_around", asks, need_flags, forbid_flags);
+    }
     bool has_component(EntityId e, uint32_t ecs_bit) { upload_if_needed(); uint32_t bits = 0; check(re_ecs_bitset(ctx_, e, &bits), "re_ecs_bitset"); return (bits >> ecs_bit) & 1u; }   // ecs_bit: RE_ECS_BIT_*
     re_ctx *context() { upload_if_needed(); return ctx_; }
 
@@ -491,6 +502,18 @@ class Pipeline {
     Row &row(EntityId e) { if (e >= rows_.size()) throw Error(RE_E_ARG, "unknown entity"); return rows_[e]; }
     void check(int rc, const char *what) { if (rc != RE_OK) throw Error(rc, std::string(what) + ": " + re_last_error(ctx_)); }
     void read(EntityId e, int component, void *dst) { upload_if_needed(); check(re_read_component(ctx_, e, component, dst), "re_read_component"); }
+    template <class Hit, class Fn> AroundAnswer<Hit> around_query(Fn fn, const char *name, const std::vector<Around> &asks, uint32_t need_flags, uint32_t forbid_flags) {
+        upload_if_needed();
+        std::vector<re_around> a; a.reserve(asks.size());
+        for (const Around &k : asks) a.push_back(re_around{ k.entity, k.reach, k.include_self ? RE_AROUND_INCLUDE_SELF : 0u, 0u });
+        const re_box_query_args args{ need_flags, forbid_flags, { 0u, 0u } };
+        AroundAnswer<Hit> out; out.status.resize(a.size());
+        uint32_t n = 0; check(fn(ctx_, a.data(), (uint32_t)a.size(), &args, nullptr, 0u, &n, out.status.data()), name);
+        out.hits.resize(n);
+        if (n) check(fn(ctx_, a.data(), (uint32_t)a.size(), &args, out.hits.data(), n, &n, out.status.data()), name);
+        out.hits.resize(std::min<size_t>(out.hits.size(), n));
+        return out;
+    }
     void upload_if_needed() {
         if (uploaded_) return;
         // Before the first executed frame every registration is collected and uploaded once (re_upload_entities REPLACES the world).  Afterwards the

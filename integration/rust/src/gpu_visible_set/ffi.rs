@@ -32,6 +32,9 @@ pub const RE_SEGMENT_NO_ENTITY: u32 = 0xFFFF_FFFF;
 #[repr(C)] #[derive(Copy, Clone)] pub struct ReSphere { pub centre: [f32; 3], pub radius: f32, pub exclude_entity: u32, pub reserved: u32 }            // 24 bytes; exclude_entity: RE_SPHERE_NO_ENTITY for none; reserved must be 0
 #[repr(C)] #[derive(Copy, Clone)] pub struct ReSphereHit { pub query: u32, pub entity_id: u32, pub dist_sq: f32, pub side: u32 }                 // 16 bytes; side bit a: beyond the minimum face of axis a, bit 4 + a: beyond the maximum face; 0: the centre is inside
 pub const RE_SPHERE_NO_ENTITY: u32 = 0xFFFF_FFFF;
+#[repr(C)] #[derive(Copy, Clone)] pub struct ReAround { pub entity_id: u32, pub reach: f32, pub flags: u32, pub reserved: u32 }                       // 16 bytes; flags: RE_AROUND_INCLUDE_SELF or 0; reserved must be 0
+pub const RE_AROUND_INCLUDE_SELF: u32 = 1;
+pub const RE_AROUND_OK: u8 = 0; pub const RE_AROUND_NOT_IN_TREE: u8 = 1; pub const RE_AROUND_TOO_LARGE: u8 = 2;                                  // status[i], one byte a query
 #[repr(C)] pub struct ReGathered { pub n_ranks: u32, pub overflowed: u32, pub counts: *const u32, pub d_entity_ids: *const u32, pub ids_rank_stride: u32,
                                    pub d_matrices: *const f32, pub matrices_rank_stride: u32 }
 #[repr(C)] #[derive(Copy, Clone, Default)] pub struct ReEntityState { pub entity_id: u32, pub model_index: u32, pub render_system: u32, pub sortable: u32, pub flags: u32,
@@ -80,6 +83,8 @@ extern "C" {
     pub fn re_query_spheres(ctx: *mut ReCtx, spheres: *const ReSphere, n: u32, args: *const ReBoxQueryArgs, hits: *mut ReSphereHit, capacity: u32, n_total: *mut u32) -> c_int;
     pub fn re_query_segments_first(ctx: *mut ReCtx, segments: *const ReSegment, n: u32, args: *const ReBoxQueryArgs, first: *mut ReSegmentHit /* [n] */, n_found: *mut u32 /* optional */) -> c_int;
     pub fn re_query_spheres_nearest(ctx: *mut ReCtx, spheres: *const ReSphere, n: u32, args: *const ReBoxQueryArgs, nearest: *mut ReSphereHit /* [n] */, n_found: *mut u32 /* optional */) -> c_int;
+    pub fn re_query_boxes_around(ctx: *mut ReCtx, asks: *const ReAround, n: u32, args: *const ReBoxQueryArgs, hits: *mut ReBoxHit, capacity: u32, n_total: *mut u32, status: *mut u8 /* nullable, [n] */) -> c_int;
+    pub fn re_query_spheres_around(ctx: *mut ReCtx, asks: *const ReAround, n: u32, args: *const ReBoxQueryArgs, hits: *mut ReSphereHit, capacity: u32, n_total: *mut u32, status: *mut u8 /* nullable, [n] */) -> c_int;
     pub fn re_wait(ctx: *mut ReCtx, vis: *mut ReVisible, tick: *mut ReTickResult) -> c_int;
     pub fn re_copy_visible(ctx: *mut ReCtx, ids: *mut u32, mats: *mut f32, capacity: u32, n_written: *mut u32) -> c_int;
     pub fn re_set_output_buffers(ctx: *mut ReCtx, d_ids: *mut u32, d_mats: *mut f32, capacity: u32) -> c_int;

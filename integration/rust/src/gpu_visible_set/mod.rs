@@ -10,7 +10,7 @@ use std::ffi::CStr;
 use std::mem::MaybeUninit;
 
 /// One resident copy of the world on one GPU.
-pub struct GpuVisibleSet { ctx: *mut ReCtx, collision_pairs: Vec<ReCollision>, logic_list: Vec<ReLogicCall>, box_hits: Vec<ReBoxHit>, segment_hits: Vec<ReSegmentHit>, sphere_hits: Vec<ReSphereHit> }
+pub struct GpuVisibleSet { ctx: *mut ReCtx, collision_pairs: Vec<ReCollision>, logic_list: Vec<ReLogicCall>, box_hits: Vec<ReBoxHit>, segment_hits: Vec<ReSegmentHit>, sphere_hits: Vec<ReSphereHit>, around_status: Vec<u8> }
 
 // the context is driven from the render thread only (Pipeline::execute), like the flows it replaces
 unsafe impl Send for GpuVisibleSet {}
@@ -51,7 +51,7 @@ impl GpuVisibleSet {
         let mut ctx: *mut ReCtx = std::ptr::null_mut();
         let rc = unsafe { re_create(&cfg, &mut ctx) };
         if rc != RE_OK { return Err(GpuError { code: rc, message: last_error(std::ptr::null()) }); }
-        Ok(GpuVisibleSet { ctx, collision_pairs: Vec::with_capacity(4096), logic_list: Vec::with_capacity(4096), box_hits: Vec::with_capacity(4096), segment_hits: Vec::with_capacity(4096), sphere_hits: Vec::with_capacity(4096) })
+        Ok(GpuVisibleSet { ctx, collision_pairs: Vec::with_capacity(4096), logic_list: Vec::with_capacity(4096), box_hits: Vec::with_capacity(4096), segment_hits: Vec::with_capacity(4096), sphere_hits: Vec::with_capacity(4096), around_status: Vec::new() })
     }
 
     fn check(&self, rc: i32) -> Result<(), GpuError> {
@@ -393,6 +393,38 @@ impl GpuVisibleSet {
         self.check(rc)?;
         unsafe { rec.set_len(spheres.len()) };                                           // the call writes all n records
         Ok(rec.into_iter().map(|h| if h.entity_id == RE_SPHERE_NO_ENTITY { None } else { Some(h) }).collect())
+    }
+
+    /// Who is within `reach` of each asking entity's box (`re_query_boxes_around`): query i is the asker's StaticAABB as it is on the device now, grown by its
+    /// reach on every side; the records are those of `entities_in_boxes` for these boxes, minus the asker (`RE_AROUND_INCLUDE_SELF` keeps it).  No `get_copy` of
+    /// the askers' components.  The second slice is the status of every ask: `RE_AROUND_OK`, or `RE_AROUND_NOT_IN_TREE` / `RE_AROUND_TOO_LARGE` and no hits for
+    /// that ask alone.  Valid at any point between calls.
+    pub fn entities_around(&mut self, asks: &[ReAround], filter: Option<&ReBoxQueryArgs>) -> Result<(&[ReBoxHit], &[u8]), GpuError> {
+        let args = filter.map_or(std::ptr::null(), |f| f as *const ReBoxQueryArgs);
+        self.around_status.resize(asks.len(), 0);
+        loop {
+            let mut n = 0u32;
+            let cap = self.box_hits.capacity() as u32;
+            let rc = unsafe { ffi::re_query_boxes_around(self.ctx, asks.as_ptr(), asks.len() as u32, args, self.box_hits.as_mut_ptr(), cap, &mut n, self.around_status.as_mut_ptr()) };
+            self.check(rc)?;
+            if n <= cap { unsafe { self.box_hits.set_len(n as usize) }; return Ok((&self.box_hits, &self.around_status)); }
+            self.box_hits = Vec::with_capacity(n as usize + n as usize / 4);            // more records than the buffer holds: once more with room
+        }
+    }
+
+    /// Who is within `reach` of each asking entity's Position (`re_query_spheres_around`): the records of `entities_within_radius` for the spheres
+    /// (Position, reach) with the asker excluded (`RE_AROUND_INCLUDE_SELF`: nobody is), dist_sq and side bit for bit; the status as `entities_around`.
+    pub fn entities_within_reach(&mut self, asks: &[ReAround], filter: Option<&ReBoxQueryArgs>) -> Result<(&[ReSphereHit], &[u8]), GpuError> {
+        let args = filter.map_or(std::ptr::null(), |f| f as *const ReBoxQueryArgs);
+        self.around_status.resize(asks.len(), 0);
+        loop {
+            let mut n = 0u32;
+            let cap = self.sphere_hits.capacity() as u32;
+            let rc = unsafe { ffi::re_query_spheres_around(self.ctx, asks.as_ptr(), asks.len() as u32, args, self.sphere_hits.as_mut_ptr(), cap, &mut n, self.around_status.as_mut_ptr()) };
+            self.check(rc)?;
+            if n <= cap { unsafe { self.sphere_hits.set_len(n as usize) }; return Ok((&self.sphere_hits, &self.around_status)); }
+            self.sphere_hits = Vec::with_capacity(n as usize + n as usize / 4);         // more records than the buffer holds: once more with room
+        }
     }
 
     /// flows/logic_flow.rs:230 + the kinematic part of :255 (update_positions, apply_change of the kinematic requests).

@@ -199,11 +199,22 @@ class SphereHit(C.Structure):
 SPHERE_DT = np.dtype([("centre", "f4", 3), ("radius", "f4"), ("exclude_entity", "u4"), ("reserved", "u4")])    # re_sphere as a numpy record
 SPHERE_HIT_DT = np.dtype([("query", "u4"), ("entity_id", "u4"), ("dist_sq", "f4"), ("side", "u4")])            # re_sphere_hit as a numpy record
 
+# re_query_boxes_around / re_query_spheres_around: re_around (16 bytes), its flag and the status bytes
+AROUND_INCLUDE_SELF = 1
+AROUND_OK, AROUND_NOT_IN_TREE, AROUND_TOO_LARGE = 0, 1, 2
+
+
+class Around(C.Structure):
+    _fields_ = [("entity_id", C.c_uint32), ("reach", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+AROUND_DT = np.dtype([("entity_id", "u4"), ("reach", "f4"), ("flags", "u4"), ("reserved", "u4")])                # re_around as a numpy record
+
 
 # every symbol include/re_hip.h declares
 EXPORTS = ["re_create", "re_destroy", "re_last_error", "re_abi_version", "re_upload_entities", "re_set_model_lod", "re_cull_pack", "re_tick",
            "re_apply_changes", "re_apply_changes_ex", "re_add_entities", "re_set_shard_range", "re_list_migrants", "re_export_entities", "re_collide",
-           "re_set_entity_types", "re_get_entity_type", "re_set_entity_logic", "re_logic_list", "re_query_boxes", "re_query_segments", "re_query_spheres", "re_query_segments_first", "re_query_spheres_nearest", "re_wait", "re_run_frames", "re_comm_unique_id", "re_comm_init", "re_comm_adopt", "re_comm_destroy", "re_allgather_visible", "re_gather_wait", "re_copy_visible", "re_set_output_buffers", "re_set_output_count", "re_read_component", "re_set_light_information", "re_ecs_bitset", "re_ecs_query", "re_visible_lights", "re_section_keys", "re_get_out_of_bounds", "re_get_stats",
+           "re_set_entity_types", "re_get_entity_type", "re_set_entity_logic", "re_logic_list", "re_query_boxes", "re_query_segments", "re_query_spheres", "re_query_segments_first", "re_query_spheres_nearest", "re_query_boxes_around", "re_query_spheres_around", "re_wait", "re_run_frames", "re_comm_unique_id", "re_comm_init", "re_comm_adopt", "re_comm_destroy", "re_allgather_visible", "re_gather_wait", "re_copy_visible", "re_set_output_buffers", "re_set_output_count", "re_read_component", "re_set_light_information", "re_ecs_bitset", "re_ecs_query", "re_visible_lights", "re_section_keys", "re_get_out_of_bounds", "re_get_stats",
            "re_debug_get_sections", "re_debug_get_shared_sections", "re_debug_get_visible_sections", "re_debug_copy_to_host", "re_get_timings", "re_get_stream",
            "re_timing_begin", "re_timing_collect", "re_get_last_candidates", "re_debug_get_plan_stats", "re_debug_live_allocations",
            "re_lighting_create", "re_lighting_destroy", "re_lighting_last_error", "re_lighting_upload_gbuffer", "re_lighting_set_lights",
@@ -266,6 +277,8 @@ def load():
     L.re_query_spheres.restype = C.c_int; L.re_query_spheres.argtypes = [vp, vp, C.c_uint32, C.POINTER(BoxQueryArgs), vp, C.c_uint32, C.POINTER(C.c_uint32)]
     L.re_query_segments_first.restype = C.c_int; L.re_query_segments_first.argtypes = [vp, vp, C.c_uint32, C.POINTER(BoxQueryArgs), vp, C.POINTER(C.c_uint32)]
     L.re_query_spheres_nearest.restype = C.c_int; L.re_query_spheres_nearest.argtypes = [vp, vp, C.c_uint32, C.POINTER(BoxQueryArgs), vp, C.POINTER(C.c_uint32)]
+    L.re_query_boxes_around.restype = C.c_int; L.re_query_boxes_around.argtypes = [vp, vp, C.c_uint32, C.POINTER(BoxQueryArgs), vp, C.c_uint32, C.POINTER(C.c_uint32), vp]
+    L.re_query_spheres_around.restype = C.c_int; L.re_query_spheres_around.argtypes = [vp, vp, C.c_uint32, C.POINTER(BoxQueryArgs), vp, C.c_uint32, C.POINTER(C.c_uint32), vp]
     L.re_apply_changes.restype = C.c_int; L.re_apply_changes.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(TickResult)]
     L.re_apply_changes_ex.restype = C.c_int; L.re_apply_changes_ex.argtypes = [vp, vp, C.c_uint32, C.POINTER(Entities), C.c_uint32, C.POINTER(TickResult)]
     L.re_add_entities.restype = C.c_int; L.re_add_entities.argtypes = [vp, C.POINTER(Entities), _u32p]

@@ -85,6 +85,11 @@ template <class Query> struct QueryFlow {
 template <class Query> struct ReducedFlow : QueryFlow<Query> {
     DevBuf<unsigned long long> d_best; std::vector<unsigned long long> winners;
 };
+// ... and one kind of tree query asked by entity (re_query_boxes_around, re_query_spheres_around): a flow of its own, and the status bytes of the last call in
+// mapped host memory -- the build kernel writes them, the host reads them behind the walk's publication.
+template <class Query> struct AroundFlow : QueryFlow<Query> {
+    Pinned status;
+};
 // Everything the kernels publish to the polling host thread lives in ONE block of mapped, coherent pinned host memory per frame lane
 // (hipHostMallocMapped | hipHostMallocCoherent): the frame result at 0, the speculation word at 128, the tick counters at 256, the
 // InstanceRange table from 8192 on.  (Round 1 used four separate mapped blocks; what made its group table arrive after
@@ -312,6 +317,7 @@ struct re_ctx : DeviceBytes, WorldState {
     ListChannel logic;
     QueryFlow<BoxQuery> boxq; QueryFlow<SegQuery> segq; QueryFlow<SphQuery> sphq;      // tree queries (re_query_boxes, re_query_segments, re_query_spheres)
     ReducedFlow<SegQuery> segfirst; ReducedFlow<SphQuery> sphnear;                     // ... and their reductions (re_query_segments_first, re_query_spheres_nearest)
+    AroundFlow<BoxQuery> boxaround; AroundFlow<SphQuery> spharound;                    // ... and the same questions asked by entity (re_query_boxes_around, re_query_spheres_around)
 };
 
 #define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return (ctx)->fail(RE_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
@@ -4061,17 +4067,8 @@ extern "C" int re_logic_list(re_ctx *c, uint32_t flags, re_logic_call *calls, ui
 static_assert(sizeof(re_box_hit) == 8 && sizeof(re_box_query_args) == 16 && sizeof(BoxQuery) == 64, "record layouts of include/re_hip.h / re_kernels.h");
 // one box as the kernel gets it; the candidate cells of all levels, counted with the kernel's own arithmetic (box_level_range)
 static uint64_t make_box_query(const float *b, uint32_t outline, uint32_t atomic, uint32_t max_level, BoxQuery *q) {
-    Aabb a = { b[0], b[1], b[2], b[3], b[4], b[5] };
-    normalize_aabb(&a, (float)outline);
-    const float lo[3] = { a.xmin, a.ymin, a.zmin }, hi[3] = { a.xmax, a.ymax, a.zmax };
-    memcpy(q->box, b, sizeof q->box); q->flags = 0; q->pad[0] = q->pad[1] = 0;
-    for (int k = 0; k < 3; k++) { q->umin[k] = f2u32(lo[k]); q->umax[k] = f2u32(hi[k]); if ((float)q->umin[k] == lo[k]) q->flags |= 1u << k; }
-    uint64_t cells = 0;
-    for (uint32_t l = 0; l <= max_level; l++) {
-        uint64_t prod = 1;
-        for (int k = 0; k < 3; k++) { uint32_t l0, h0; box_level_range(q->umin[k], q->umax[k], (q->flags >> k) & 1u, atomic << l, &l0, &h0); prod *= (uint64_t)(h0 - l0 + 1u); }
-        cells += prod;
-    }
+    memcpy(q->box, b, sizeof q->box); q->pad[0] = q->pad[1] = 0;
+    const uint64_t cells = box_query_record(b, outline, atomic, max_level, q->umin, q->umax, &q->flags);      // (re_kernels.h: shared with the device builder)
     q->ncells = (uint32_t)std::min<uint64_t>(cells, 0xFFFFFFFFull);
     return cells;
 }
@@ -4278,3 +4275,65 @@ extern "C" int re_query_spheres_nearest(re_ctx *c, const re_sphere *spheres, uin
     auto build = [&](uint32_t i, SphQuery *out) { return build_sphere_query(c, "re_query_spheres_nearest", spheres, i, margin, out); };
     return run_tree_query_reduced(c, "re_query_spheres_nearest", "spheres", "spheres", "nearest", c->sphnear, spheres, n, args, nearest, n_found, build, k_sphere_nearest_reduce, k_sphere_nearest_pick, A);
 } RE_ABI_GUARD(c, "re_query_spheres_nearest")
+
+// ... and the same two questions asked by entity: "who is within reach of me" (DESIGN.md section 4.8).  The asker's StaticAABB and Position exist on the device
+// only, so the host sends rows and a small kernel builds the records there (k_around_build_*, re_treequery.hip); the walk follows in the same stream, with no
+// host wait in between, and publishes once.  An ask travels in the head of the 64-byte query record that replaces it, so the batch goes through
+// prepare_tree_query like its siblings'.  What the host cannot know -- the asker is not in the tree, its box covers too many cells -- comes back as a status byte.
+static_assert(sizeof(re_around) == 16 && sizeof(AroundAsk) == 16 && RE_AROUND_INCLUDE_SELF == AROUND_INCLUDE_SELF && RE_AROUND_OK == AROUND_OK && RE_AROUND_NOT_IN_TREE == AROUND_NOT_IN_TREE &&
+              RE_AROUND_TOO_LARGE == AROUND_TOO_LARGE && RE_SPHERE_NO_ENTITY == AROUND_NO_ENTITY, "record layouts and values of include/re_hip.h / re_kernels.h");
+template <class Query, class KArgs>
+static int run_around_query(re_ctx *c, const char *call, AroundFlow<Query> &F, bool spheres, const re_around *asks, uint32_t n, const re_box_query_args *args, void *hits, uint32_t capacity,
+                            uint32_t *n_total, uint8_t *status, uint32_t rec_words, void (*build_kernel)(AroundBuildArgs), void (*walk)(KArgs), KArgs A) {
+    if (c->h_res) {
+        HIPCHK(c, hipSetDevice(c->device));
+        { int rc = settle_frame(c); if (rc != RE_OK) return rc; }              // first: a tick in flight may remove an asker (out of bounds), and the asks are checked against the rows as they are
+        if (n <= RE_BOX_QUERY_MAX_QUERIES && F.status.bytes < n) {             // (replaced only after the stream has drained: the last call's build kernel wrote into it)
+            HIPCHK(c, sync_stream(c->stream));
+            HIPCHK(c, F.status.alloc(std::max<size_t>((size_t)n + n / 2, 256), hipHostMallocMapped | hipHostMallocCoherent));
+        }
+    }
+    const float limit = 64.0f * (float)c->cfg.outline_length;
+    auto build = [&](uint32_t i, Query *out) {
+        const re_around &a = asks[i];
+        if (a.reserved) return c->fail(RE_E_ARG, "%s: ask %u: reserved must be 0", call, i);
+        if (a.flags & ~RE_AROUND_INCLUDE_SELF) return c->fail(RE_E_ARG, "%s: ask %u has unknown flag bits (0x%x)", call, i, a.flags);
+        if (!std::isfinite(a.reach) || a.reach < 0.0f) return c->fail(RE_E_ARG, "%s: ask %u: the reach is not finite or negative", call, i);
+        if (spheres && a.reach > limit) return c->fail(RE_E_ARG, "%s: ask %u: the reach lies beyond 64 outline lengths", call, i);      // (as re_query_spheres refuses the radius)
+        uint32_t row = 0;
+        if (!c->row_of(a.entity_id, &row) || row >= c->n || (c->h_flags[row] & F_DEAD)) return c->fail(RE_E_ARG, "%s: ask %u: unknown entity %u", call, i, a.entity_id);
+        memset(out, 0, sizeof *out);
+        const AroundAsk ask{ row, a.reach, a.flags, 0u };
+        memcpy(out, &ask, sizeof ask);
+        return (int)RE_OK;
+    };
+    bool launch = false;
+    { int rc = prepare_tree_query(c, call, "asks", "asks", capacity && !hits ? "capacity without a buffer" : nullptr, F, asks, n, args, n_total, build, rec_words, capacity, nullptr, A, &launch); if (rc != RE_OK) return rc; }
+    if (!launch) {                                                             // no ask, or a world without sections: nobody is in the tree
+        if (status && n) memset(status, RE_AROUND_NOT_IN_TREE, n);
+        return RE_OK;
+    }
+    AroundBuildArgs B{};
+    B.n = n; B.nrows = c->n; B.outline = c->cfg.outline_length; B.atomic = c->cfg.atomic_length; B.max_level = c->maxlevel; B.max_cells = RE_BOX_QUERY_MAX_CELLS;
+    B.margin = segment_query_margin(c->cfg.outline_length);
+    B.row_flags = c->d_flags.p; B.row_cell = c->d_row_cell.p; B.row_id = c->d_id.p; B.row_aabb = c->d_aabb.p; B.row_pos = c->d_pos.p;
+    B.q = F.d_q.p; B.status = F.status.template dev<uint8_t>();
+    hipLaunchKernelGGL(build_kernel, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, B);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(walk, dim3(tree_query_grid(n, A.n_sh_chunks)), dim3(BOXQ_THREADS), 0, c->stream, A);
+    HIPCHK(c, hipGetLastError());
+    uint32_t nrec = 0;
+    { int rc = F.ch.wait(c, A.seq, &nrec); if (rc != RE_OK) return rc; }
+    if (status) memcpy(status, F.status.template host<uint8_t>(), n);        // (the build kernel ended before the walk began, the walk has published)
+    return read_out_list(c, nrec, F.d_out.p, rec_words * sizeof(unsigned long long), hits, A.capacity, n_total);
+}
+extern "C" int re_query_boxes_around(re_ctx *c, const re_around *asks, uint32_t n, const re_box_query_args *args, re_box_hit *hits, uint32_t capacity, uint32_t *n_total, uint8_t *status) try {
+    if (!c) return RE_E_ARG;
+    return run_around_query(c, "re_query_boxes_around", c->boxaround, false, asks, n, args, hits, capacity, n_total, status, 1u, k_around_build_boxes, k_box_query_around, BoxQueryArgs{});
+} RE_ABI_GUARD(c, "re_query_boxes_around")
+extern "C" int re_query_spheres_around(re_ctx *c, const re_around *asks, uint32_t n, const re_box_query_args *args, re_sphere_hit *hits, uint32_t capacity, uint32_t *n_total, uint8_t *status) try {
+    if (!c) return RE_E_ARG;
+    SphQueryArgs A{};
+    A.outline = c->cfg.outline_length; A.margin = segment_query_margin(c->cfg.outline_length);
+    return run_around_query(c, "re_query_spheres_around", c->spharound, true, asks, n, args, hits, capacity, n_total, status, 2u, k_around_build_spheres, k_sphere_query, A);
+} RE_ABI_GUARD(c, "re_query_spheres_around")

@@ -440,6 +440,26 @@ RE_HD void box_level_range(uint32_t umin, uint32_t umax, bool whole, uint32_t le
     if (whole && l > 0u && l * len == umin) l -= 1u;
     *lo = l; *hi = udiv_len(umax, len);
 }
+// The record arithmetic of a query box b (xmin xmax ymin ymax zmin zmax), in one place for the host builders (make_box_query, re_api.hip) and the device
+// builder (k_around_build_*, re_treequery.hip), so that the two cannot diverge: the clip to the world, the truncation, the whole-number flags, and the
+// candidate cells over all levels by box_level_range.  Compares, fminf / fmaxf, conversions and integer arithmetic only: nothing a compiler contracts.
+RE_HD uint64_t box_query_record(const float *b, uint32_t outline, uint32_t atomic, uint32_t max_level, uint32_t *umin, uint32_t *umax, uint32_t *flags) {
+    Aabb a = { b[0], b[1], b[2], b[3], b[4], b[5] };
+    normalize_aabb(&a, (float)outline);
+    const float lo[3] = { a.xmin, a.ymin, a.zmin }, hi[3] = { a.xmax, a.ymax, a.zmax };
+    uint32_t fl = 0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) { umin[k] = f2u32(lo[k]); umax[k] = f2u32(hi[k]); if ((float)umin[k] == lo[k]) fl |= 1u << k; }
+    *flags = fl;
+    uint64_t cells = 0;
+    for (uint32_t l = 0; l <= max_level; l++) {
+        uint64_t prod = 1;
+#pragma unroll
+        for (int k = 0; k < 3; k++) { uint32_t l0, h0; box_level_range(umin[k], umax[k], (fl >> k) & 1u, atomic << l, &l0, &h0); prod *= (uint64_t)(h0 - l0 + 1u); }
+        cells += prod;
+    }
+    return cells;
+}
 constexpr uint32_t BOXQ_THREADS = 256, BOXQ_PROBES = 4;      // probes a lane makes per round: 1024 candidate cells a round
 constexpr uint32_t BOXQ_QUEUE = BOXQ_THREADS * BOXQ_PROBES;   // hit sections of one round (each probe yields at most one)
 constexpr uint32_t BOXQ_HITBUF = 1024;                        // records a workgroup stages in LDS between two flushes (more go out one wave at a time)
@@ -494,6 +514,27 @@ __global__ void k_segment_first_reduce(SegBestArgs A);
 __global__ void k_segment_first_pick(SegBestArgs A);
 __global__ void k_sphere_nearest_reduce(SphBestArgs A);
 __global__ void k_sphere_nearest_pick(SphBestArgs A);
+// ... and the same questions asked by entity (re_query_boxes_around, re_query_spheres_around): the asker's StaticAABB and Position live on the device only, so
+// the query records are built there.  The host resolves id -> row and leaves an ask in the first 16 bytes of each 64-byte query record it uploads;
+// k_around_build_* (one lane an ask) reads the row's live state and writes the whole BoxQuery / SphQuery record in its place -- what make_box_query /
+// build_sphere_query write for the same geometry, by box_query_record -- and one status byte.  The walk follows in the stream.
+//   boxes: (min - reach, max + reach) per axis of the stored StaticAABB, one f32 subtraction / addition each; the asker's id in pad[0] (k_box_query_around
+//     leaves it out; AROUND_NO_ENTITY: nobody);
+//   spheres: centre = Position, r2 = reach * reach, the bounding cube (c - r) - m, (c + r) + m, exclude = the asker (k_sphere_query as it is).
+// A refused ask (not in the tree; too many candidate cells; a centre beyond 64 outline lengths, which re_query_spheres refuses) leaves the empty record:
+// ncells = 0, umin = 2 * (atomic << max_level), umax = umin - 1 -- every level's cell range of the unique part is empty (umin is a multiple of every
+// section length) and no cell of the grid reaches beyond umin in the shared part --, an inverted box / r2 = -1, which no entity passes.
+struct AroundAsk { uint32_t row; float reach; uint32_t flags, pad; };
+constexpr uint32_t AROUND_INCLUDE_SELF = 1u, AROUND_NO_ENTITY = 0xFFFFFFFFu;
+constexpr uint8_t AROUND_OK = 0, AROUND_NOT_IN_TREE = 1, AROUND_TOO_LARGE = 2;
+struct AroundBuildArgs {
+    uint32_t n, nrows, outline, atomic, max_level, max_cells; float margin;
+    const uint32_t *row_flags, *row_cell, *row_id; const Aabb *row_aabb; const float *row_pos;
+    void *q; uint8_t *status;               // q: n 64-byte records, asks on entry; status: mapped host memory, read behind the walk's publication
+};
+__global__ void k_around_build_boxes(AroundBuildArgs B);
+__global__ void k_around_build_spheres(AroundBuildArgs B);
+__global__ void k_box_query_around(BoxQueryArgs A);
 hipError_t sort_pairs_u64_u32(void *tmp, size_t *tmp_bytes, const uint64_t *keys_in, uint64_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out,
                               uint32_t n, unsigned begin_bit, unsigned end_bit, hipStream_t stream);      // re_sort.hip (rocPRIM radix sort)
 __global__ void k_rb_ovl_insert(uint32_t n, const Pair64 *pairs, RbTables T);

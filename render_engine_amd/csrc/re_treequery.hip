@@ -4,6 +4,8 @@
 // and "who is within r of this point" -- an explosion, a proximity trigger (k_sphere_query).
 // One walk of the tree, written once over a query shape and a mode of storing hits; the three kernels instantiate it with the default mode (every hit a record), and
 // the four kernels of re_query_segments_first / re_query_spheres_nearest with the other two: reduce the hits' keys per query, then pick the winners (TreeqMode, below).
+// The same questions asked by entity (re_query_boxes_around, re_query_spheres_around) have their records built here, from the askers' rows
+// (k_around_build_*, at the end), and are walked by k_box_query_around -- the boxes' shape with the asker left out -- and by k_sphere_query as it is.
 //
 // The rule of the boxes: (query i, entity) for every live entity in the tree (not F_DEAD, not an F_PHANTOM replica, row_cell set; ghost instances of the
 // frozen static cache are no entities) whose stored StaticAABB intersects box i by StaticAABB::intersect (aabb.rs:68-73: closed intervals, plain f32
@@ -74,6 +76,30 @@ struct BoxShape {
     // Records are read by the host as soon as it has seen the count: write-through stores (sc1), as k_logic_list's.
     static __device__ __forceinline__ void store(const Args &A, uint32_t slot, const Rec &rec) {
         if (slot < A.capacity) __hip_atomic_store(&A.out[slot], rec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
+
+// ... and the box of an asking entity (re_query_boxes_around): the same records, the same test, minus the asker, whose id the device builder left in pad[0].
+// A shape of its own, so that k_box_query stays the code object it is.  The prune lets everything through but the builder's empty record (an inverted box),
+// which walks nothing.
+struct BoxAroundShape : BoxShape {
+    static constexpr uint32_t TILE_WORDS = 14;     // umin[3], umax[3], flags, the box (6 floats), exclude
+    uint32_t exclude;
+    static __device__ __forceinline__ void stage(BoxAroundShape &L, const Query &Q, uint32_t tid) {
+        if (tid < 6u) L.box[tid] = Q.box[tid];
+        if (tid == 6u) L.exclude = Q.pad[0];
+    }
+    static __device__ __forceinline__ void to_tile(const Query &Q, uint32_t *t) { BoxShape::to_tile(Q, t); t[6] = Q.pad[0]; }
+    static __device__ __forceinline__ BoxAroundShape from_tile(const uint32_t *t) {
+        BoxAroundShape P;
+#pragma unroll
+        for (int a = 0; a < 6; a++) P.box[a] = __uint_as_float(t[a]);
+        P.exclude = t[6];
+        return P;
+    }
+    __device__ __forceinline__ bool misses(const CellBox &) const { return box[0] > box[1]; }
+    __device__ __forceinline__ bool test(const Aabb &a, const uint32_t *id, uint32_t query, Rec &rec) const {
+        return *id != exclude && BoxShape::test(a, id, query, rec);
     }
 };
 
@@ -488,7 +514,73 @@ template <class Shape, int Mode = TREEQ_ALL, class KArgs> __device__ __forceinli
 }
 static_assert(BOXQ_TILE == BOXQ_THREADS, "one lane per tile query");
 
+// ---- the queries asked by entity: the records are built here ---------------------------------------------------------------------------------------
+// One lane per ask (AroundAsk, re_kernels.h): the row's live flags, row_cell and StaticAABB / Position make the record the host builders would make for the
+// same geometry -- box_query_record is theirs --, written over the ask.  The box and cube bounds and r2 are single rounded operations (__fsub_rn, __fadd_rn,
+// __fmul_rn: what the host's plain f32 arithmetic does).  No loop but the levels', no LDS, nothing shared between lanes.
+template <bool Spheres> __device__ __forceinline__ void around_build(const AroundBuildArgs &B) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B.n) return;
+    void *rec = static_cast<char *>(B.q) + (size_t)i * 64u;
+    const AroundAsk ask = *static_cast<const AroundAsk *>(rec);            // (read before the record takes its place)
+    const float inf = __builtin_inff();
+    uint8_t status = AROUND_NOT_IN_TREE;
+    uint32_t id = AROUND_NO_ENTITY;
+    float bb[6] = { inf, -inf, inf, -inf, inf, -inf }, ctr[3] = { 0.0f, 0.0f, 0.0f };
+    if (ask.row < B.nrows && !(B.row_flags[ask.row] & (F_DEAD | F_PHANTOM)) && B.row_cell[ask.row] != ROW_CELL_NONE) {      // an entity of the tree (a halo replica's owner answers)
+        status = AROUND_OK;
+        id = B.row_id[ask.row];
+        if constexpr (Spheres) {
+            const float limit = 64.0f * (float)B.outline;                  // re_query_spheres refuses a centre beyond it: the margin covers the rounding below it only
+#pragma unroll
+            for (int a = 0; a < 3; a++) {
+                ctr[a] = B.row_pos[(size_t)ask.row * 3u + a];
+                if (!(fabsf(ctr[a]) <= limit)) status = AROUND_TOO_LARGE;
+                bb[2 * a] = __fsub_rn(__fsub_rn(ctr[a], ask.reach), B.margin); bb[2 * a + 1] = __fadd_rn(__fadd_rn(ctr[a], ask.reach), B.margin);
+            }
+        } else {
+            const Aabb s = B.row_aabb[ask.row];
+            bb[0] = __fsub_rn(s.xmin, ask.reach); bb[1] = __fadd_rn(s.xmax, ask.reach); bb[2] = __fsub_rn(s.ymin, ask.reach); bb[3] = __fadd_rn(s.ymax, ask.reach);
+            bb[4] = __fsub_rn(s.zmin, ask.reach); bb[5] = __fadd_rn(s.zmax, ask.reach);
+        }
+    }
+    uint32_t umin[3], umax[3], flags = 0u, ncells = 0u;
+    if (status == AROUND_OK) {
+        const uint64_t cells = box_query_record(bb, B.outline, B.atomic, B.max_level, umin, umax, &flags);
+        if (cells > B.max_cells) status = AROUND_TOO_LARGE; else ncells = (uint32_t)cells;
+    }
+    if (status != AROUND_OK) {                                             // the empty record (re_kernels.h)
+        const uint32_t top = 2u * (B.atomic << B.max_level);
+#pragma unroll
+        for (int a = 0; a < 3; a++) { umin[a] = top; umax[a] = top - 1u; bb[2 * a] = inf; bb[2 * a + 1] = -inf; }
+        flags = 0u; ncells = 0u;
+    }
+    const uint32_t exclude = (ask.flags & AROUND_INCLUDE_SELF) ? AROUND_NO_ENTITY : id;
+    if constexpr (Spheres) {
+        SphQuery q;
+        q.r2 = status == AROUND_OK ? __fmul_rn(ask.reach, ask.reach) : -1.0f;
+        q.exclude = exclude; q.flags = flags; q.ncells = ncells; q.pad[0] = q.pad[1] = q.pad[2] = 0u;
+#pragma unroll
+        for (int a = 0; a < 3; a++) { q.c[a] = ctr[a]; q.umin[a] = umin[a]; q.umax[a] = umax[a]; }
+        *static_cast<SphQuery *>(rec) = q;
+    } else {
+        BoxQuery q;
+#pragma unroll
+        for (int a = 0; a < 6; a++) q.box[a] = bb[a];
+#pragma unroll
+        for (int a = 0; a < 3; a++) { q.umin[a] = umin[a]; q.umax[a] = umax[a]; }
+        q.flags = flags; q.ncells = ncells; q.pad[0] = exclude; q.pad[1] = 0u;
+        *static_cast<BoxQuery *>(rec) = q;
+    }
+    B.status[i] = status;
+}
+static_assert(sizeof(BoxQuery) == 64 && sizeof(SphQuery) == 64 && sizeof(AroundAsk) == 16, "an ask lies in the head of its 64-byte query record");
+
 }  // namespace
+
+__global__ __launch_bounds__(256) void k_around_build_boxes(AroundBuildArgs B) { around_build<false>(B); }
+__global__ __launch_bounds__(256) void k_around_build_spheres(AroundBuildArgs B) { around_build<true>(B); }
+__global__ __launch_bounds__(BOXQ_THREADS) void k_box_query_around(BoxQueryArgs A) { __shared__ TreeqShared<BoxAroundShape> S; treeq_kernel<BoxAroundShape>(A, S); }
 
 __global__ __launch_bounds__(BOXQ_THREADS) void k_box_query(BoxQueryArgs A) { __shared__ TreeqShared<BoxShape> S; treeq_kernel<BoxShape>(A, S); }
 __global__ __launch_bounds__(BOXQ_THREADS) void k_segment_query(SegQueryArgs A) { __shared__ TreeqShared<SegShape> S; treeq_kernel<SegShape>(A, S); }

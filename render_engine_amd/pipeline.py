@@ -496,6 +496,36 @@ class Pipeline:
             sph["exclude_entity"] = _capi.SPHERE_NO_ENTITY if exclude is None else np.asarray(exclude, np.uint32)
         return self._reduced_query(self._L.re_query_spheres_nearest, "re_query_spheres_nearest", sph, need, forbid, _capi.SPHERE_HIT_DT)
 
+    def _around_query(self, fn, name, ids, reach, include_self, need_flags, forbid_flags, capacity, dtype):
+        """the tree queries asked by entity fn(ctx, asks, n, args, records, capacity, &n_total, status): the two-call idiom of _record_list, with the status
+        bytes of the call that filled the records"""
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        asks = np.zeros(len(ids), _capi.AROUND_DT)
+        asks["entity_id"], asks["reach"] = ids, np.asarray(reach, np.float32)
+        asks["flags"] = np.where(np.broadcast_to(np.asarray(include_self, bool), ids.shape), _capi.AROUND_INCLUDE_SELF, 0)
+        args = _capi.BoxQueryArgs(int(need_flags), int(forbid_flags)) if (need_flags or forbid_flags) else None
+        n = C.c_uint32()
+        status = np.zeros(max(len(ids), 1), np.uint8)
+        if capacity is None:
+            self._check(fn(self._h, asks.ctypes.data, len(asks), args, None, 0, C.byref(n), None), name)
+            capacity = n.value
+        rec = np.zeros(max(capacity, 1), dtype)
+        self._check(fn(self._h, asks.ctypes.data, len(asks), args, rec.ctypes.data, capacity, C.byref(n), status.ctypes.data), name)
+        return rec[:min(n.value, capacity)].copy(), n.value, status[:len(ids)].copy()
+
+    def find_entities_around(self, ids, reach, include_self=False, need_flags=0, forbid_flags=0, capacity=None):
+        """who is within `reach` of each asking entity's box (re_query_boxes_around): query i is the asker's StaticAABB as it is on the device now, grown by
+        reach[i] (a scalar or one per asker) on every side; (hits, n_total, status) with hits a BOX_HIT_DT array exactly as find_entities_in_boxes reports
+        for those boxes, minus the asker (include_self, a bool or one per asker, keeps it), and status[i] AROUND_OK, AROUND_NOT_IN_TREE or AROUND_TOO_LARGE
+        (no hits for that asker, the others are answered).  No read-back of the askers' components.  Valid at any point between calls."""
+        return self._around_query(self._L.re_query_boxes_around, "re_query_boxes_around", ids, reach, include_self, need_flags, forbid_flags, capacity, _capi.BOX_HIT_DT)
+
+    def find_entities_within_reach(self, ids, reach, include_self=False, need_flags=0, forbid_flags=0, capacity=None):
+        """who is within `reach` of each asking entity's Position (re_query_spheres_around): (hits, n_total, status) with hits a SPHERE_HIT_DT array exactly as
+        find_entities_within_radius reports for the spheres (Position, reach[i]) with the asker excluded (include_self: nobody is), and status as
+        find_entities_around.  Valid at any point between calls."""
+        return self._around_query(self._L.re_query_spheres_around, "re_query_spheres_around", ids, reach, include_self, need_flags, forbid_flags, capacity, _capi.SPHERE_HIT_DT)
+
     # -- multi-GPU exchange (RCCL behind the C ABI) ---------------------------------------------------
     @staticmethod
     def comm_unique_id():
